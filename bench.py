@@ -13,9 +13,17 @@ per GPU over RCCL; ranks read RANK/LOCAL_RANK/WORLD_SIZE from the env.
 
 value = prod(size_global) * elem_size / t_step / 2^30 (whole-job effective
 GiB/s; inputs resident in HBM when the timed region starts).  Also emitted:
-`roofline` (dominant kernel, HIP-event timed, algorithmic bytes vs the 8 TB/s
-HBM peak) and `cpu_baseline` (the C oracle restatement timed on this box's
-host cores, rank 0 at N=1 only).
+`roofline` (dominant kernel, HIP-event timed over the same timed region,
+algorithmic bytes vs the 8 TB/s HBM peak).
+
+A plain run does only what the headline needs: set up, warm up, time the
+steps, print the line.  `--full` adds everything that takes runs of its own:
+the checksum self-verification (`verify`), the per-stage HIP-event step
+(`stage_ms`), the identity-layout variant (`variant_identity`, N=1) and
+`cpu_baseline` (the C oracle restatement timed on the host cores, rank 0 at
+N=1 only).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (a fixed seeded sample when the output is large); the inputs
+are seeded, so two builds can be compared output for output.
 """
 
 import argparse
@@ -71,7 +79,15 @@ def parse_args():
                     help="split the RCCL exchange into N chunks and unpack "
                          "each as it lands (the reference's Waitany overlap; "
                          "1 = single grouped exchange)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs: checksum verification, "
+                         "per-stage timing step, identity-layout variant "
+                         "and CPU baseline (N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as "
+                         "DIR/<name>.npy (seeded sample if large)")
     return ap.parse_args()
 
 
@@ -102,6 +118,28 @@ def cpu_baseline(sample=(512, 512, 512), reps=8):
         }
     except Exception:
         return None
+
+
+# --dump-outputs budget: 32 MiB per run in all, split over ranks and arrays
+DUMP_BUDGET_BYTES = 32 << 20
+DUMP_SEED = 0x5EED
+
+
+def dump_output(dirname, name, ten, budget_bytes):
+    """Write `ten` (1-D device tensor) as dirname/name.npy in float32/float64
+    (complex as interleaved re,im).  Outputs above the budget are sampled at
+    a fixed seeded set of element indices, identical from run to run."""
+    import numpy as np
+    n = ten.numel()
+    keep = max(1, budget_bytes // ten.element_size())
+    if n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(
+            0, n, size=keep, dtype=np.int64))
+        ten = ten.index_select(0, torch.from_numpy(idx).to(ten.device))
+    if ten.is_complex():
+        ten = torch.view_as_real(ten)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), ten.cpu().numpy())
 
 
 def main():
@@ -150,9 +188,10 @@ def main():
                              device=device))
     src = PencilArray(Pi, rank, src_t)
 
-    def measure(permuted):
-        """One full measurement (setup + warmup + timed region + verify +
-        stage times) of the x->y (or x->y->z) transpose; returns a dict."""
+    def measure(permuted, dump_dir=None):
+        """One measurement (setup + warmup + timed region; with --full also
+        verify + stage times) of the x->y (or x->y->z) transpose; returns a
+        dict."""
         po_perm = (1, 2, 0) if (permuted or args.double) else None
         Po = Pencil(topo, dims, (0, 2), permute=po_perm)
         Pz = (Pencil(topo, dims, (0, 1), permute=(2, 1, 0))
@@ -210,6 +249,27 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
 
+        # what the last timed step left in the output arrays
+        if dump_dir:
+            outs = [("dst", dst.data)]
+            if t2 is not None:
+                outs.append(("dstz", dstz.data))
+            for name, ten in outs:
+                if world > 1:
+                    name = f"{name}_rank{rank}"
+                dump_output(dump_dir, name, ten,
+                            DUMP_BUDGET_BYTES // (world * len(outs)))
+
+        if not args.full:
+            return {
+                "elapsed": elapsed,
+                "gpu_ms": gpu_ms,
+                "verify": None,
+                "stage_ms": None,
+                "permuted": permuted,
+                "nproc_sub": t._native.native.nproc_sub,
+            }
+
         # Per-stage HIP-event times (TimerOutputs analogue): one extra
         # untimed step with timing events enabled, AFTER the timed region.
         stage_ms = None
@@ -255,11 +315,11 @@ def main():
             "nproc_sub": t._native.native.nproc_sub,
         }
 
-    m = measure(args.permuted)
+    m = measure(args.permuted, dump_dir=args.dump_outputs)
     # the identity-layout variant (at 1x1: a straight device copy) measured
     # alongside the headline when it differs from it (N=1 default runs)
     variant = None
-    if n_gpus == 1 and args.permuted and not args.double:
+    if args.full and n_gpus == 1 and args.permuted and not args.double:
         mi = measure(False)
         variant = {
             "workload": "identity memory layout (collapses to device copy)",
@@ -328,7 +388,7 @@ def main():
         }
 
     cb = None
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline()
 
     sz = "x".join(map(str, dims))

@@ -1,7 +1,7 @@
 # Time the N>1 pack/unpack descriptors (8-GPU 1024^3 x->y shapes) standalone
 # via pa_device_copy + HIP events: the HBM legs of the multi-GPU roofline.
-import ctypes, sys, torch
-sys.path.insert(0, "/root/repo")
+import ctypes, os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pencilarrays_amd import Topology, Pencil, build_plan, native
 
 lib = native.load()

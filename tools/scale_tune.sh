@@ -19,7 +19,7 @@ STEPS=${2:-10}
 run() {
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
     --master-addr 127.0.0.1 --master-port 29604 bench.py \
-    --gpus "$N" --steps "$STEPS" --warmup 3 --no-cpu-baseline "$@" \
+    --gpus "$N" --steps "$STEPS" --warmup 3 --full --no-cpu-baseline "$@" \
     2>/dev/null | tail -1
 }
 
