@@ -154,6 +154,27 @@ pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
                          int64_t elem_size, const void *src, void *dst,
                          void *stream);
 
+/* Which kernel pa_device_copy / a plan would launch for this descriptor
+ * (host-only, needs no GPU; the launcher executes exactly this decision).
+ * src/dst are used for their alignment only and never dereferenced.
+ * out = {kind, word_bytes, byteified (0/1), sweep_depth}: word_bytes is the
+ * width of the word the kernel moves per element of its (possibly
+ * word-scaled) descriptor; byteified = the descriptor went through the
+ * byte-ify fallback (element sizes that are no power of two <= 16);
+ * sweep_depth = tiles swept per workgroup (1 for non-tile kernels). */
+#define PA_KERNEL_NONE      0   /* empty descriptor */
+#define PA_KERNEL_COPY_1D   1
+#define PA_KERNEL_COPY_1D_NT 2
+#define PA_KERNEL_LINEAR    3
+#define PA_KERNEL_TILE      4   /* scalar LDS tile */
+#define PA_KERNEL_TILE_VS   5   /* 8-byte vector-store tile */
+#define PA_KERNEL_TILE_PK   6   /* packed 1-/2-byte tile */
+#define PA_KERNEL_GENERIC   7
+pa_status pa_copy_kernel_kind(int nd, const int64_t *dims, const int64_t *sstr,
+                              int64_t soff, const int64_t *dstr, int64_t doff,
+                              int64_t elem_size, const void *src,
+                              const void *dst, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

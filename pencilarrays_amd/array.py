@@ -48,8 +48,10 @@ class PencilArray:
 
     @classmethod
     def empty(cls, pencil: Pencil, rank: int, dtype="float64",
-              extra_dims: Tuple[int, ...] = (), backend: str = "numpy",
+              extra_dims: Tuple[int, ...] = (), backend: Optional[str] = None,
               device=None):
+        if backend is None:  # a device implies torch storage
+            backend = "numpy" if device is None else "torch"
         mem = tuple(pencil.size_local(rank, memory_order=True)) + tuple(extra_dims)
         n = math.prod(mem)
         if backend == "numpy":

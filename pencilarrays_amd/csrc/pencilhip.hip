@@ -319,6 +319,131 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs(
     }
 }
 
+/* LDS-tiled transpose for 1- and 2-byte elements with PACKED (8-B) global
+ * accesses on both sides.  V = 8/sizeof(T) elements per access.  Each lane
+ * owns a VxV micro-block: it loads V rows (consecutive ta) of 8 B of
+ * consecutive axis-0 elements, transposes the block in registers, and
+ * writes V 8-B LDS words, each holding V consecutive ta elements of one
+ * axis-0 row.  The store phase reads one 8-B LDS word per lane and stores it
+ * as 8 B of consecutive ta elements — no 1-/2-byte global access on the
+ * aligned path.  The caller guarantees that soff, doff and every stride
+ * except the two unit ones are multiples of V and both base pointers are
+ * 8-B aligned, so every wide access is aligned.  Micro-blocks cut by the
+ * tile edge (extents that are no multiple of V) load and store element by
+ * element inside the same kernel.
+ *
+ * LDS layout: row i holds TJ/V 8-B words; word column jb is stored at
+ * jb ^ ((i/V) % (TJ/V)), no padding.  Expected bank-conflict degree: none.
+ * Write (8-B LDS store, 16-lane groups, 32 banks): the 16 lanes of a group
+ * hold 16 consecutive i-blocks of one jb, the row pitch is a multiple of
+ * 32 dwords, so the XOR spreads them over 16 distinct dword pairs.  Read
+ * (8-B LDS load, 32-lane groups, 64 banks): a group reads 256 contiguous
+ * bytes (one 2-byte row or two adjacent 1-byte rows), each word once. */
+template <typename T, int TI, int TJ, int NTHR>
+__global__ __launch_bounds__(NTHR) void k_transpose_tile_pk(
+    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
+    int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+{
+    static_assert(sizeof(T) == 1 || sizeof(T) == 2, "packed tile: 1/2-byte");
+    constexpr int V = 8 / (int)sizeof(T);
+    constexpr int B = 8 * (int)sizeof(T); /* bits per element */
+    constexpr int NBI = TI / V, NBJ = TJ / V;
+    static_assert(TI % V == 0 && TJ % V == 0, "tile must be whole blocks");
+    static_assert(NBI % 16 == 0 && NBJ % 16 == 0 && (NBJ & (NBJ - 1)) == 0,
+                  "bank analysis assumes 16-block groups, pow2 columns");
+    static_assert((NBI * NBJ) % NTHR == 0 && (TI * NBJ) % NTHR == 0,
+                  "whole passes per workgroup");
+    constexpr uint64_t EMASK = ((uint64_t)1 << B) - 1;
+
+    __shared__ uint64_t tile[TI * NBJ];
+
+    const int tid = threadIdx.x;
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int64_t t_i = bid % ntile_i;
+    int64_t rest = bid / ntile_i;
+    const int64_t t_j = rest % ntile_j;
+    int64_t batch = rest / ntile_j;
+
+    int64_t so_b = d.soff, do_b = d.doff;
+    for (int a = 1; a < d.nd; a++) {
+        if (a == ta) continue;
+        const int64_t j = batch % d.dims[a];
+        batch /= d.dims[a];
+        so_b += j * d.sstr[a];
+        do_b += j * d.dstr[a];
+    }
+
+    const int64_t i0 = t_i * TI;
+    const int ni = (int)(d.dims[0] - i0 < TI ? d.dims[0] - i0 : TI);
+    const int64_t j0 = t_j * TJ;
+    const int nj = (int)(d.dims[ta] - j0 < TJ ? d.dims[ta] - j0 : TJ);
+
+    /* load + in-register transpose + LDS write, one micro-block per pass */
+    {
+        const int64_t sj = d.sstr[ta];
+        const T *base = src + so_b + i0 + j0 * sj;
+#pragma unroll
+        for (int it = 0; it < NBI * NBJ / NTHR; it++) {
+            const int mb = tid + it * NTHR;
+            const int bi = mb % NBI, bj = mb / NBI;
+            const int ib = bi * V, jb = bj * V;
+            if (ib >= ni || jb >= nj) continue; /* never read back */
+            uint64_t in[V];
+            const T *p = base + (int64_t)jb * sj + ib;
+            if (ib + V <= ni && jb + V <= nj) {
+#pragma unroll
+                for (int r = 0; r < V; r++)
+                    in[r] = *(const uint64_t *)(p + (int64_t)r * sj);
+            } else { /* block cut by the tile edge: element loads */
+#pragma unroll
+                for (int r = 0; r < V; r++) {
+                    uint64_t w = 0;
+                    if (jb + r < nj) {
+#pragma unroll
+                        for (int k = 0; k < V; k++)
+                            if (ib + k < ni)
+                                w |= (uint64_t)p[(int64_t)r * sj + k]
+                                     << (k * B);
+                    }
+                    in[r] = w;
+                }
+            }
+            const int col = bj ^ (bi & (NBJ - 1));
+#pragma unroll
+            for (int k = 0; k < V; k++) {
+                uint64_t o = 0;
+#pragma unroll
+                for (int r = 0; r < V; r++)
+                    o |= ((in[r] >> (k * B)) & EMASK) << (r * B);
+                tile[(ib + k) * NBJ + col] = o;
+            }
+        }
+    }
+    __syncthreads();
+    /* store: lanes sweep 8-B words along ta, passes sweep axis 0 */
+    {
+        const int64_t di = d.dstr[0];
+        T *base = dst + do_b + j0 + i0 * di;
+#pragma unroll 4
+        for (int it = 0; it < TI * NBJ / NTHR; it++) {
+            const int c = tid + it * NTHR;
+            const int bj = c % NBJ, i = c / NBJ;
+            const int jb = bj * V;
+            if (i >= ni || jb >= nj) continue;
+            const uint64_t v = tile[i * NBJ + (bj ^ ((i / V) & (NBJ - 1)))];
+            T *p = base + (int64_t)i * di + jb;
+            if (jb + V <= nj) {
+                *(uint64_t *)p = v;
+            } else { /* ta tail shorter than one word: element stores */
+#pragma unroll
+                for (int r = 0; r < V; r++)
+                    if (jb + r < nj) p[r] = (T)(v >> (r * B));
+            }
+        }
+    }
+}
+
 /* ================= descriptor normalization & dispatch ============= */
 
 struct CopyDescH {
@@ -427,12 +552,35 @@ static int grid_for(int64_t work_items, int per_block)
     return (int)blocks;
 }
 
-static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
-                             const void *src, void *dst, hipStream_t stream)
+/* The outcome of the dispatch decision: which kernel runs, on which
+ * (possibly word-scaled or byte-ified) descriptor.  select_kernel() is the
+ * ONE place the decision is made; launch_sel() only executes it and
+ * pa_copy_kernel_kind() only reports it. */
+struct KernelSel {
+    int kind = PA_KERNEL_NONE;
+    int word = 0;      /* bytes per kernel word */
+    int byteified = 0; /* went through the byte-ify fallback */
+    int sweep = 1;     /* j-tiles swept per workgroup (tile kernels) */
+    int ta = -1;       /* dst-contiguous axis (tile kernels) */
+    CopyDescH d;       /* the descriptor the kernel runs, in `word` units */
+};
+
+/* sweep depth of the 4-/8-byte tiles: long sweeps win on tall-skinny shapes
+ * (+1.5% A/B) but must keep >= ~4k workgroups for occupancy and tail
+ * balance on small/batched shapes */
+static int sweep_depth(int64_t nti, int64_t ntj, int64_t nbatch)
 {
+    if (ntj * nti * nbatch >= 32 * 4096 && ntj >= 256) return 32;
+    if (ntj * nti * nbatch >= 8 * 4096 && ntj >= 64) return 8;
+    return 1;
+}
+
+static pa_status select_kernel(const CopyDescH &dn, int64_t esz,
+                               const void *src, const void *dst,
+                               KernelSel *out)
+{
+    *out = KernelSel();
     if (dn.total == 0) return 0;
-    const char *s = (const char *)src;
-    char *d = (char *)dst;
 
     const bool lin = (dn.sstr[0] == 1 && dn.dstr[0] == 1);
     if (lin) {
@@ -445,55 +593,14 @@ static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
             if (!word_scale(dn, esz, 1, &w)) return fail("word_scale(1)");
             W = 1;
         }
-        if (w.nd == 1) {
-            dim3 blocks;
-            pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
-            if (gst) return gst;
-            if (W == 16 && w.total * 16 >= (512ll << 20))
-                hipLaunchKernelGGL(k_copy_1d_nt, blocks, dim3(256),
-                                   0, stream, (const uint4 *)s + w.soff,
-                                   (uint4 *)d + w.doff, w.total);
-            else if (W == 16)
-                hipLaunchKernelGGL(k_copy_1d<uint4>, blocks, dim3(256),
-                                   0, stream, (const uint4 *)s + w.soff,
-                                   (uint4 *)d + w.doff, w.total);
-            else if (W == 8)
-                hipLaunchKernelGGL(k_copy_1d<uint64_t>, blocks,
-                                   dim3(256), 0, stream,
-                                   (const uint64_t *)s + w.soff,
-                                   (uint64_t *)d + w.doff, w.total);
-            else if (W == 4)
-                hipLaunchKernelGGL(k_copy_1d<uint32_t>, blocks,
-                                   dim3(256), 0, stream,
-                                   (const uint32_t *)s + w.soff,
-                                   (uint32_t *)d + w.doff, w.total);
-            else
-                hipLaunchKernelGGL(k_copy_1d<uint8_t>, blocks, dim3(256),
-                                   0, stream, (const uint8_t *)s + w.soff,
-                                   (uint8_t *)d + w.doff, w.total);
-        } else {
-            DescDev dd = to_dev(w);
-            dim3 blocks;
-            pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
-            if (gst) return gst;
-            if (W == 16)
-                hipLaunchKernelGGL(k_copy_linear<uint4>, blocks,
-                                   dim3(256), 0, stream, (const uint4 *)s,
-                                   (uint4 *)d, dd);
-            else if (W == 8)
-                hipLaunchKernelGGL(k_copy_linear<uint64_t>, blocks,
-                                   dim3(256), 0, stream, (const uint64_t *)s,
-                                   (uint64_t *)d, dd);
-            else if (W == 4)
-                hipLaunchKernelGGL(k_copy_linear<uint32_t>, blocks,
-                                   dim3(256), 0, stream, (const uint32_t *)s,
-                                   (uint32_t *)d, dd);
-            else
-                hipLaunchKernelGGL(k_copy_linear<uint8_t>, blocks,
-                                   dim3(256), 0, stream, (const uint8_t *)s,
-                                   (uint8_t *)d, dd);
-        }
-        HIP_CHECK(hipGetLastError());
+        out->word = (int)W;
+        out->d = w;
+        if (w.nd == 1)
+            out->kind = (W == 16 && w.total * 16 >= (512ll << 20))
+                            ? PA_KERNEL_COPY_1D_NT
+                            : PA_KERNEL_COPY_1D;
+        else
+            out->kind = PA_KERNEL_LINEAR;
         return 0;
     }
 
@@ -503,117 +610,58 @@ static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
         for (int a = 1; a < dn.nd; a++)
             if (dn.dstr[a] == 1) { ta = a; break; }
 
-    if (ta > 0 && (esz == 4 || esz == 8 || esz == 16)) {
-        DescDev dd = to_dev(dn);
+    const bool pow2 = esz == 1 || esz == 2 || esz == 4 || esz == 8 ||
+                      esz == 16;
+    if (ta > 0 && pow2) {
         int64_t nbatch = 1;
         for (int a = 1; a < dn.nd; a++)
             if (a != ta) nbatch *= dn.dims[a];
+        out->word = (int)esz;
+        out->d = dn;
+        out->ta = ta;
         /* tile shapes probe-measured on MI355X (profiles/r01_probe_copy*,
          * r2_probe_kernels*): 8-B elements prefer the 64x128 vector-store
          * tile (+1.5-1.8% median) when alignment permits; otherwise (and
-         * for 4-B) the scalar 128(i)x64(j) r16 sweep; 16-B: 32x32. */
-        bool vec_ok = false;
+         * for 4-B) the scalar 128(i)x64(j) r16 sweep; 16-B: 32x32.
+         * 1-/2-B elements take the packed 128x128 tile when every 8-B
+         * access is aligned, else the scalar 128x64 tile. */
         if (esz == 8) {
-            vec_ok = ((dn.doff & 1) == 0) && ((dn.dstr[0] & 1) == 0) &&
-                     (((uintptr_t)d & 15) == 0);
+            bool vec_ok = ((dn.doff & 1) == 0) && ((dn.dstr[0] & 1) == 0) &&
+                          (((uintptr_t)dst & 15) == 0);
             for (int a2 = 1; a2 < dn.nd && vec_ok; a2++)
                 if (a2 != ta && (dn.dstr[a2] & 1)) vec_ok = false;
+            if (vec_ok) {
+                out->kind = PA_KERNEL_TILE_VS;
+                out->sweep = sweep_depth((dn.dims[0] + 63) / 64,
+                                         (dn.dims[ta] + 127) / 128, nbatch);
+                return 0;
+            }
         }
-        if (vec_ok) {
-            constexpr int TI = 64, TJ = 128, NR = 16;
-            const int64_t nti = (dn.dims[0] + TI - 1) / TI;
-            const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
-            int jc = 1; /* same occupancy/tail-balance thresholds as below */
-            if (ntj * nti * nbatch >= 32 * 4096 && ntj >= 256)
-                jc = 32;
-            else if (ntj * nti * nbatch >= 8 * 4096 && ntj >= 64)
-                jc = 8;
-            const int64_t njc = (ntj + jc - 1) / jc;
-            const int64_t nblocks = nti * njc * nbatch;
-            dim3 grid;
-            pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-            if (gst) return gst;
-#define LAUNCH_VS(JCV)                                                       \
-    hipLaunchKernelGGL((k_transpose_tile_vs<uint64_t, TI, TJ, NR, JCV>),     \
-                       grid, dim3(64, NR), 0, stream, (const uint64_t *)s,   \
-                       (uint64_t *)d, dd, ta, nti, njc, nblocks)
-            if (jc == 32)
-                LAUNCH_VS(32);
-            else if (jc == 8)
-                LAUNCH_VS(8);
-            else
-                LAUNCH_VS(1);
-#undef LAUNCH_VS
-            HIP_CHECK(hipGetLastError());
+        if (esz <= 2) {
+            const int64_t V = 8 / esz;
+            bool pk_ok = (dn.soff % V == 0) && (dn.doff % V == 0) &&
+                         (((uintptr_t)src & 7) == 0) &&
+                         (((uintptr_t)dst & 7) == 0) &&
+                         (dn.dstr[0] % V == 0);
+            for (int a2 = 1; a2 < dn.nd && pk_ok; a2++) {
+                if (dn.sstr[a2] % V) pk_ok = false;
+                if (a2 != ta && dn.dstr[a2] % V) pk_ok = false;
+            }
+            out->kind = pk_ok ? PA_KERNEL_TILE_PK : PA_KERNEL_TILE;
             return 0;
         }
-        if (esz == 8 || esz == 4) {
-            constexpr int TI = 128, TJ = 64, NR = 16;
-            const int64_t nti = (dn.dims[0] + TI - 1) / TI;
-            const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
-            /* adaptive sweep depth: long sweeps win on tall-skinny shapes
-             * (+1.5% A/B) but must keep >= ~4k workgroups for occupancy and
-             * tail balance on small/batched shapes */
-            int jc = 1;
-            if (ntj * nti * nbatch >= 32 * 4096 && ntj >= 256)
-                jc = 32;
-            else if (ntj * nti * nbatch >= 8 * 4096 && ntj >= 64)
-                jc = 8;
-            const int64_t njc = (ntj + jc - 1) / jc;
-            const int64_t nblocks = nti * njc * nbatch;
-            dim3 grid;
-            pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-            if (gst) return gst;
-#define LAUNCH_TT(T, JCV)                                                        hipLaunchKernelGGL((k_transpose_tile<T, TI, TJ, NR, JCV>), grid,                                dim3(64, NR), 0, stream, (const T *)s, (T *)d, dd,                           ta, nti, njc, nblocks)
-            if (esz == 8) {
-                if (jc == 32)
-                    LAUNCH_TT(uint64_t, 32);
-                else if (jc == 8)
-                    LAUNCH_TT(uint64_t, 8);
-                else
-                    LAUNCH_TT(uint64_t, 1);
-            } else {
-                if (jc == 32)
-                    LAUNCH_TT(uint32_t, 32);
-                else if (jc == 8)
-                    LAUNCH_TT(uint32_t, 8);
-                else
-                    LAUNCH_TT(uint32_t, 1);
-            }
-#undef LAUNCH_TT
-        } else {
-            constexpr int TI = 32, TJ = 32, NR = 8, JC = 1;
-            const int64_t nti = (dn.dims[0] + TI - 1) / TI;
-            const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
-            const int64_t nblocks = nti * ntj * nbatch;
-            dim3 grid;
-            pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-            if (gst) return gst;
-            hipLaunchKernelGGL((k_transpose_tile<uint4, TI, TJ, NR, JC>),
-                               grid, dim3(64, NR), 0, stream,
-                               (const uint4 *)s, (uint4 *)d, dd, ta, nti, ntj,
-                               nblocks);
-        }
-        HIP_CHECK(hipGetLastError());
+        out->kind = PA_KERNEL_TILE;
+        if (esz == 8 || esz == 4)
+            out->sweep = sweep_depth((dn.dims[0] + 127) / 128,
+                                     (dn.dims[ta] + 63) / 64, nbatch);
         return 0;
     }
 
     /* generic fallback */
-    if (esz == 16 || esz == 8 || esz == 4) {
-        DescDev dd = to_dev(dn);
-        const dim3 blocks(grid_for(dn.total, 256)); /* grid-stride kernel */
-        if (esz == 16)
-            hipLaunchKernelGGL(k_copy_generic<uint4>, blocks, dim3(256),
-                               0, stream, (const uint4 *)s, (uint4 *)d, dd);
-        else if (esz == 8)
-            hipLaunchKernelGGL(k_copy_generic<uint64_t>, blocks,
-                               dim3(256), 0, stream, (const uint64_t *)s,
-                               (uint64_t *)d, dd);
-        else
-            hipLaunchKernelGGL(k_copy_generic<uint32_t>, blocks,
-                               dim3(256), 0, stream, (const uint32_t *)s,
-                               (uint32_t *)d, dd);
-        HIP_CHECK(hipGetLastError());
+    if (pow2) {
+        out->kind = PA_KERNEL_GENERIC;
+        out->word = (int)esz;
+        out->d = dn;
         return 0;
     }
 
@@ -634,8 +682,233 @@ static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
         }
         CopyDescH b = normalize_desc(dn.nd + 1, dims, ss, dn.soff * esz, ds,
                                      dn.doff * esz);
-        return launch_desc(b, 1, src, dst, stream);
+        pa_status st = select_kernel(b, 1, src, dst, out);
+        out->byteified = 1;
+        return st;
     }
+}
+
+template <typename T>
+static pa_status launch_tile(const KernelSel &k, const char *s, char *d,
+                             hipStream_t stream)
+{
+    constexpr int TI = 128, TJ = 64, NR = 16;
+    const CopyDescH &dn = k.d;
+    const int ta = k.ta;
+    DescDev dd = to_dev(dn);
+    int64_t nbatch = 1;
+    for (int a = 1; a < dn.nd; a++)
+        if (a != ta) nbatch *= dn.dims[a];
+    const int64_t nti = (dn.dims[0] + TI - 1) / TI;
+    const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
+    const int64_t njc = (ntj + k.sweep - 1) / k.sweep;
+    const int64_t nblocks = nti * njc * nbatch;
+    dim3 grid;
+    pa_status gst = grid2d(nblocks, 64 * NR, &grid);
+    if (gst) return gst;
+#define LAUNCH_TT(JCV)                                                       \
+    hipLaunchKernelGGL((k_transpose_tile<T, TI, TJ, NR, JCV>), grid,         \
+                       dim3(64, NR), 0, stream, (const T *)s, (T *)d, dd,    \
+                       ta, nti, njc, nblocks)
+    if constexpr (sizeof(T) >= 4) {
+        if (k.sweep == 32)
+            LAUNCH_TT(32);
+        else if (k.sweep == 8)
+            LAUNCH_TT(8);
+        else
+            LAUNCH_TT(1);
+    } else {
+        LAUNCH_TT(1);
+    }
+#undef LAUNCH_TT
+    return 0;
+}
+
+template <typename T>
+static pa_status launch_tile_pk(const KernelSel &k, const char *s, char *d,
+                                hipStream_t stream)
+{
+    constexpr int TI = 128, TJ = 128, NT = 256;
+    const CopyDescH &dn = k.d;
+    const int ta = k.ta;
+    DescDev dd = to_dev(dn);
+    int64_t nbatch = 1;
+    for (int a = 1; a < dn.nd; a++)
+        if (a != ta) nbatch *= dn.dims[a];
+    const int64_t nti = (dn.dims[0] + TI - 1) / TI;
+    const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
+    const int64_t nblocks = nti * ntj * nbatch;
+    dim3 grid;
+    pa_status gst = grid2d(nblocks, NT, &grid);
+    if (gst) return gst;
+    hipLaunchKernelGGL((k_transpose_tile_pk<T, TI, TJ, NT>), grid, dim3(NT),
+                       0, stream, (const T *)s, (T *)d, dd, ta, nti, ntj,
+                       nblocks);
+    return 0;
+}
+
+static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
+                            hipStream_t stream)
+{
+    const char *s = (const char *)src;
+    char *d = (char *)dst;
+    const CopyDescH &w = k.d;
+    const int W = k.word;
+    pa_status st = 0;
+
+    switch (k.kind) {
+    case PA_KERNEL_NONE:
+        return 0;
+    case PA_KERNEL_COPY_1D:
+    case PA_KERNEL_COPY_1D_NT: {
+        dim3 blocks;
+        pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
+        if (gst) return gst;
+        if (k.kind == PA_KERNEL_COPY_1D_NT)
+            hipLaunchKernelGGL(k_copy_1d_nt, blocks, dim3(256),
+                               0, stream, (const uint4 *)s + w.soff,
+                               (uint4 *)d + w.doff, w.total);
+        else if (W == 16)
+            hipLaunchKernelGGL(k_copy_1d<uint4>, blocks, dim3(256),
+                               0, stream, (const uint4 *)s + w.soff,
+                               (uint4 *)d + w.doff, w.total);
+        else if (W == 8)
+            hipLaunchKernelGGL(k_copy_1d<uint64_t>, blocks,
+                               dim3(256), 0, stream,
+                               (const uint64_t *)s + w.soff,
+                               (uint64_t *)d + w.doff, w.total);
+        else if (W == 4)
+            hipLaunchKernelGGL(k_copy_1d<uint32_t>, blocks,
+                               dim3(256), 0, stream,
+                               (const uint32_t *)s + w.soff,
+                               (uint32_t *)d + w.doff, w.total);
+        else
+            hipLaunchKernelGGL(k_copy_1d<uint8_t>, blocks, dim3(256),
+                               0, stream, (const uint8_t *)s + w.soff,
+                               (uint8_t *)d + w.doff, w.total);
+        break;
+    }
+    case PA_KERNEL_LINEAR: {
+        DescDev dd = to_dev(w);
+        dim3 blocks;
+        pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
+        if (gst) return gst;
+        if (W == 16)
+            hipLaunchKernelGGL(k_copy_linear<uint4>, blocks,
+                               dim3(256), 0, stream, (const uint4 *)s,
+                               (uint4 *)d, dd);
+        else if (W == 8)
+            hipLaunchKernelGGL(k_copy_linear<uint64_t>, blocks,
+                               dim3(256), 0, stream, (const uint64_t *)s,
+                               (uint64_t *)d, dd);
+        else if (W == 4)
+            hipLaunchKernelGGL(k_copy_linear<uint32_t>, blocks,
+                               dim3(256), 0, stream, (const uint32_t *)s,
+                               (uint32_t *)d, dd);
+        else
+            hipLaunchKernelGGL(k_copy_linear<uint8_t>, blocks,
+                               dim3(256), 0, stream, (const uint8_t *)s,
+                               (uint8_t *)d, dd);
+        break;
+    }
+    case PA_KERNEL_TILE_VS: {
+        constexpr int TI = 64, TJ = 128, NR = 16;
+        const int ta = k.ta;
+        DescDev dd = to_dev(w);
+        int64_t nbatch = 1;
+        for (int a = 1; a < w.nd; a++)
+            if (a != ta) nbatch *= w.dims[a];
+        const int64_t nti = (w.dims[0] + TI - 1) / TI;
+        const int64_t ntj = (w.dims[ta] + TJ - 1) / TJ;
+        const int64_t njc = (ntj + k.sweep - 1) / k.sweep;
+        const int64_t nblocks = nti * njc * nbatch;
+        dim3 grid;
+        pa_status gst = grid2d(nblocks, 64 * NR, &grid);
+        if (gst) return gst;
+#define LAUNCH_VS(JCV)                                                       \
+    hipLaunchKernelGGL((k_transpose_tile_vs<uint64_t, TI, TJ, NR, JCV>),     \
+                       grid, dim3(64, NR), 0, stream, (const uint64_t *)s,   \
+                       (uint64_t *)d, dd, ta, nti, njc, nblocks)
+        if (k.sweep == 32)
+            LAUNCH_VS(32);
+        else if (k.sweep == 8)
+            LAUNCH_VS(8);
+        else
+            LAUNCH_VS(1);
+#undef LAUNCH_VS
+        break;
+    }
+    case PA_KERNEL_TILE:
+        if (W == 16) {
+            constexpr int TI = 32, TJ = 32, NR = 8, JC = 1;
+            const int ta = k.ta;
+            DescDev dd = to_dev(w);
+            int64_t nbatch = 1;
+            for (int a = 1; a < w.nd; a++)
+                if (a != ta) nbatch *= w.dims[a];
+            const int64_t nti = (w.dims[0] + TI - 1) / TI;
+            const int64_t ntj = (w.dims[ta] + TJ - 1) / TJ;
+            const int64_t nblocks = nti * ntj * nbatch;
+            dim3 grid;
+            pa_status gst = grid2d(nblocks, 64 * NR, &grid);
+            if (gst) return gst;
+            hipLaunchKernelGGL((k_transpose_tile<uint4, TI, TJ, NR, JC>),
+                               grid, dim3(64, NR), 0, stream,
+                               (const uint4 *)s, (uint4 *)d, dd, ta, nti, ntj,
+                               nblocks);
+        } else if (W == 8)
+            st = launch_tile<uint64_t>(k, s, d, stream);
+        else if (W == 4)
+            st = launch_tile<uint32_t>(k, s, d, stream);
+        else if (W == 2)
+            st = launch_tile<uint16_t>(k, s, d, stream);
+        else
+            st = launch_tile<uint8_t>(k, s, d, stream);
+        if (st) return st;
+        break;
+    case PA_KERNEL_TILE_PK:
+        st = W == 2 ? launch_tile_pk<uint16_t>(k, s, d, stream)
+                    : launch_tile_pk<uint8_t>(k, s, d, stream);
+        if (st) return st;
+        break;
+    case PA_KERNEL_GENERIC: {
+        DescDev dd = to_dev(w);
+        const dim3 blocks(grid_for(w.total, 256)); /* grid-stride kernel */
+        if (W == 16)
+            hipLaunchKernelGGL(k_copy_generic<uint4>, blocks, dim3(256),
+                               0, stream, (const uint4 *)s, (uint4 *)d, dd);
+        else if (W == 8)
+            hipLaunchKernelGGL(k_copy_generic<uint64_t>, blocks,
+                               dim3(256), 0, stream, (const uint64_t *)s,
+                               (uint64_t *)d, dd);
+        else if (W == 4)
+            hipLaunchKernelGGL(k_copy_generic<uint32_t>, blocks,
+                               dim3(256), 0, stream, (const uint32_t *)s,
+                               (uint32_t *)d, dd);
+        else if (W == 2)
+            hipLaunchKernelGGL(k_copy_generic<uint16_t>, blocks,
+                               dim3(256), 0, stream, (const uint16_t *)s,
+                               (uint16_t *)d, dd);
+        else
+            hipLaunchKernelGGL(k_copy_generic<uint8_t>, blocks,
+                               dim3(256), 0, stream, (const uint8_t *)s,
+                               (uint8_t *)d, dd);
+        break;
+    }
+    default:
+        return fail("bad kernel kind %d", k.kind);
+    }
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
+                             const void *src, void *dst, hipStream_t stream)
+{
+    KernelSel k;
+    pa_status st = select_kernel(dn, esz, src, dst, &k);
+    if (st) return st;
+    return launch_sel(k, src, dst, stream);
 }
 
 /* ================= metadata ======================================== */
@@ -1639,6 +1912,24 @@ pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
     if (nd <= 0 || nd > MAXND) return fail("bad nd");
     CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
     return launch_desc(d, elem_size, src, dst, (hipStream_t)stream);
+}
+
+pa_status pa_copy_kernel_kind(int nd, const int64_t *dims, const int64_t *sstr,
+                              int64_t soff, const int64_t *dstr, int64_t doff,
+                              int64_t elem_size, const void *src,
+                              const void *dst, int64_t out[4])
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (elem_size <= 0) return fail("bad elem_size");
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    KernelSel k;
+    pa_status st = select_kernel(d, elem_size, src, dst, &k);
+    if (st) return st;
+    out[0] = k.kind;
+    out[1] = k.word;
+    out[2] = k.byteified;
+    out[3] = k.sweep;
+    return 0;
 }
 
 } /* extern "C" */

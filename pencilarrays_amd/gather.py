@@ -18,6 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .array import PencilArray
+from .dtypes import bits_dtype, to_numpy
 
 MPI_TAG = 42  # gather.jl:23
 
@@ -27,17 +28,21 @@ def _logical_block(x: PencilArray) -> np.ndarray:
     the inverse-permuted copy of gather.jl:32-40."""
     lv = x.logical_view()
     if x.is_torch:
-        lv = lv.cpu().numpy()
+        lv = to_numpy(lv)
     return np.ascontiguousarray(lv)
 
 
 def gather_sim(arrays: Sequence[PencilArray]) -> np.ndarray:
+    """Global logical-order array from all ranks' PencilArrays.  Torch data
+    of a dtype numpy cannot represent (``torch.bfloat16``) comes back as the
+    same-width unsigned-integer bit pattern (``uint16``), placed exactly as
+    ``int16`` data would be."""
     p0 = arrays[0].pencil
     extra = arrays[0].extra_dims
     shape = tuple(p0.size_global) + extra
     first = arrays[0].data
     dtype = first.dtype if isinstance(first, np.ndarray) else \
-        np.dtype(str(first.dtype).replace("torch.", ""))
+        bits_dtype(first.dtype)
     dest = np.empty(shape, dtype=dtype)
     for r, x in enumerate(arrays):
         assert x.rank == r
@@ -49,11 +54,17 @@ def gather_sim(arrays: Sequence[PencilArray]) -> np.ndarray:
 
 
 def gather_dist(x: PencilArray, root: int = 0) -> Optional[np.ndarray]:
+    """Distributed gather to ``root`` (None elsewhere).  As in
+    :func:`gather_sim`, torch dtypes without a numpy counterpart
+    (``torch.bfloat16``) are gathered as ``uint16`` bit patterns."""
     import torch
     import torch.distributed as dist
 
     comm_rank = dist.get_rank()
     block = _logical_block(x)
+    out_dtype = block.dtype
+    if out_dtype == np.uint16 and x.is_torch:
+        block = block.view(np.int16)  # bit patterns travel as int16
 
     if comm_rank != root:
         dist.send(torch.from_numpy(block), dst=root, tag=MPI_TAG)
@@ -62,17 +73,17 @@ def gather_dist(x: PencilArray, root: int = 0) -> Optional[np.ndarray]:
     p = x.pencil
     extra = x.extra_dims
     shape = tuple(p.size_global) + extra
-    dest = np.empty(shape, dtype=block.dtype)
+    dest = np.empty(shape, dtype=out_dtype)
     topo = p.topology
     for r in range(topo.nranks):
         region = p.axes_for_rank(r)
         sl = tuple(slice(lo, hi) for lo, hi in region) + \
             tuple(slice(None) for _ in extra)
         if r == root:
-            dest[sl] = block
+            dest[sl] = block.view(out_dtype)
         else:
             dims = tuple(hi - lo for lo, hi in region) + extra
             buf = torch.empty(dims, dtype=torch.from_numpy(block).dtype)
             dist.recv(buf, src=r, tag=MPI_TAG)
-            dest[sl] = buf.numpy()
+            dest[sl] = buf.numpy().view(out_dtype)
     return dest

@@ -8,7 +8,7 @@ reference.  This is what PencilFFTs' in-place plans use."""
 from __future__ import annotations
 
 import math
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -19,7 +19,9 @@ from .pencil import Pencil
 class ManyPencilArray:
     def __init__(self, pencils: Sequence[Pencil], rank: int,
                  dtype="float64", extra_dims: Tuple[int, ...] = (),
-                 backend: str = "numpy", device=None):
+                 backend: Optional[str] = None, device=None):
+        if backend is None:  # a device implies torch storage
+            backend = "numpy" if device is None else "torch"
         extra_dims = tuple(int(e) for e in extra_dims)
         pex = math.prod(extra_dims) if extra_dims else 1
         lengths = [p.length_local(rank) * pex for p in pencils]

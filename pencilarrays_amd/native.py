@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 I64 = ctypes.c_int64
 I32 = ctypes.c_int32
@@ -51,6 +51,53 @@ def load() -> ctypes.CDLL:
 def _check(lib, status: int, what: str):
     if status != 0:
         raise RuntimeError(f"{what}: {lib.pa_last_error().decode()}")
+
+
+# kernel kinds reported by pa_copy_kernel_kind (include/pencilhip.h)
+KERNEL_NONE = 0
+KERNEL_COPY_1D = 1
+KERNEL_COPY_1D_NT = 2
+KERNEL_LINEAR = 3
+KERNEL_TILE = 4
+KERNEL_TILE_VS = 5
+KERNEL_TILE_PK = 6
+KERNEL_GENERIC = 7
+KERNEL_NAMES = {
+    KERNEL_NONE: "NONE", KERNEL_COPY_1D: "COPY_1D",
+    KERNEL_COPY_1D_NT: "COPY_1D_NT", KERNEL_LINEAR: "LINEAR",
+    KERNEL_TILE: "TILE", KERNEL_TILE_VS: "TILE_VS",
+    KERNEL_TILE_PK: "TILE_PK", KERNEL_GENERIC: "GENERIC",
+}
+
+
+class KernelKind(NamedTuple):
+    kind: int
+    word_bytes: int
+    byteified: int
+    sweep_depth: int
+
+
+def copy_kernel_kind(desc, esz: int, src_ptr: int = 0,
+                     dst_ptr: int = 0) -> KernelKind:
+    """Which kernel ``pa_device_copy`` / a plan launches for ``desc`` with
+    ``esz``-byte elements (host-only, no GPU needed).  ``desc`` is a
+    ``plan.CopyDesc`` or the ``(dims, sstr, soff, dstr, doff)`` tuple of
+    ``NativePlan.copydesc``.  The pointers are used for their alignment
+    only and never dereferenced."""
+    lib = load()
+    if hasattr(desc, "sstrides"):
+        dims, sstr, soff, dstr, doff = (desc.dims, desc.sstrides,
+                                        desc.soffset, desc.dstrides,
+                                        desc.doffset)
+    else:
+        dims, sstr, soff, dstr, doff = desc
+    nd = len(dims)
+    out = (I64 * 4)()
+    _check(lib, lib.pa_copy_kernel_kind(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), I64(esz), VP(src_ptr), VP(dst_ptr),
+        out), "pa_copy_kernel_kind")
+    return KernelKind(*(int(v) for v in out))
 
 
 class NativePlan:

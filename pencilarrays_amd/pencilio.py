@@ -36,6 +36,7 @@ from typing import Tuple
 import numpy as np
 
 from .array import PencilArray
+from .dtypes import numpy_dtype
 from .permutations import is_identity, perm_apply
 
 MPIIO_VERSION = "0.9.4"
@@ -50,13 +51,28 @@ _JULIA_TYPES = {
 _NUMPY_TYPES = {v: k for k, v in _JULIA_TYPES.items()}
 
 
+def _unsupported(name: str) -> TypeError:
+    return TypeError(
+        f"MPIIODriver: unsupported element type {name} (supported: "
+        f"{sorted(_JULIA_TYPES)})")
+
+
 def _julia_type(dtype: np.dtype) -> str:
     try:
         return _JULIA_TYPES[dtype.name]
     except KeyError:
-        raise TypeError(
-            f"MPIIODriver: unsupported element type {dtype.name} (supported: "
-            f"{sorted(_JULIA_TYPES)})") from None
+        raise _unsupported(dtype.name) from None
+
+
+def _data_dtype(data) -> np.dtype:
+    """numpy element type of a PencilArray's data (numpy or torch); torch
+    dtypes numpy cannot represent (bfloat16) are unsupported on disk."""
+    if isinstance(data, np.ndarray):
+        return data.dtype
+    dt = numpy_dtype(data.dtype)
+    if dt is None:
+        raise _unsupported(str(data.dtype).replace("torch.", ""))
+    return dt
 
 
 def _barrier():
@@ -117,6 +133,8 @@ class MPIIOFile:
         """setindex!(file, x, name; chunks) (mpi_io.jl:172-189)."""
         p = x.pencil
         offset = self.position
+        dtype = _data_dtype(x.data)
+        _julia_type(dtype)  # unsupported types fail before touching the file
         esz = x.data.dtype.itemsize if isinstance(x.data, np.ndarray) else \
             x.data.element_size()
         size_bytes = (math.prod(p.size_global)
@@ -129,7 +147,6 @@ class MPIIOFile:
 
         local = x.data if isinstance(x.data, np.ndarray) else \
             x.data.cpu().numpy()
-        dtype = local.dtype
         n = p.ndims
         e = len(x.extra_dims)
 
@@ -192,8 +209,7 @@ class MPIIOFile:
         if meta is None:
             raise KeyError(f"dataset '{name}' not found")
         p = x.pencil
-        dtype = (x.data.dtype if isinstance(x.data, np.ndarray)
-                 else np.dtype(str(x.data.dtype).replace("torch.", "")))
+        dtype = _data_dtype(x.data)
         if meta["element_type"] != _julia_type(dtype):
             raise TypeError(
                 f"incompatible type of file and array: "
@@ -224,8 +240,7 @@ class MPIIOFile:
 
     def read_raw(self, x: PencilArray, offset: int = 0):
         """read!(file, x; offset) without metadata (mpi_io.jl:265-278)."""
-        dtype = (x.data.dtype if isinstance(x.data, np.ndarray)
-                 else np.dtype(str(x.data.dtype).replace("torch.", "")))
+        dtype = _data_dtype(x.data)
         self._read_at(x, offset, False, np.dtype(dtype))
         return x
 
