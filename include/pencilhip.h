@@ -93,6 +93,22 @@ void pa_comm_destroy(pa_comm *c);
 pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
                          int64_t elem_size, int e, const int64_t *extra_dims,
                          int rank, int flags, pa_plan **out);
+/* Composite elements: an element of ncomp scalars of scalar_size bytes each,
+ * COMPONENTS FASTEST (array of structs) — the reference's isbits element
+ * types such as SVector{3,Float64}, which it transposes as one 24-byte
+ * element (test/ode.jl).  scalar_size must be 1, 2, 4, 8 or 16 when
+ * ncomp > 1.  Every descriptor, offset and count of the plan stays in ELEMENT
+ * units; only byte sizes (staging buffers, exchange) carry the factor
+ * scalar_size * ncomp.  pa_plan_create(.., elem_size, ..) is exactly
+ * pa_plan_create_comp(.., elem_size, 1, ..).
+ * A host with a composite element should pass the pair — (8, 3) for
+ * SVector{3,Float64} — rather than elem_size = 24: the pair reaches the
+ * wide-element LDS tile (PA_KERNEL_TILE_WIDE), while a plain composite
+ * elem_size keeps the byte-ify fallback. */
+pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
+                              int64_t scalar_size, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              pa_plan **out);
 void pa_plan_destroy(pa_plan *p);
 
 /* Subgroup communicator for the exchange (required when the subgroup size
@@ -153,6 +169,14 @@ pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
                          int64_t soff, const int64_t *dstr, int64_t doff,
                          int64_t elem_size, const void *src, void *dst,
                          void *stream);
+/* The same for composite elements (see pa_plan_create_comp): strides,
+ * offsets and dims in elements of scalar_size * ncomp bytes.
+ * pa_device_copy is the ncomp = 1 case. */
+pa_status pa_device_copy_comp(int nd, const int64_t *dims,
+                              const int64_t *sstr, int64_t soff,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp,
+                              const void *src, void *dst, void *stream);
 
 /* Which kernel pa_device_copy / a plan would launch for this descriptor
  * (host-only, needs no GPU; the launcher executes exactly this decision).
@@ -170,10 +194,29 @@ pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
 #define PA_KERNEL_TILE_VS   5   /* 8-byte vector-store tile */
 #define PA_KERNEL_TILE_PK   6   /* packed 1-/2-byte tile */
 #define PA_KERNEL_GENERIC   7
+#define PA_KERNEL_TILE_WIDE 8   /* wide-element tile: m words per element */
 pa_status pa_copy_kernel_kind(int nd, const int64_t *dims, const int64_t *sstr,
                               int64_t soff, const int64_t *dstr, int64_t doff,
                               int64_t elem_size, const void *src,
                               const void *dst, int64_t out[4]);
+/* Composite-element form; pa_copy_kernel_kind is its ncomp = 1 case and the
+ * first four fields mean the same.  out = {kind, word_bytes, byteified,
+ * sweep_depth, words_per_element}.  With B = scalar_size * ncomp, ncomp > 1:
+ *  - B in {1,2,4,8,16}: the decision of elem_size = B;
+ *  - linear at element level: COPY_1D / COPY_1D_NT / LINEAR in the widest
+ *    word dividing the run bytes, every byte stride/offset and both bases;
+ *  - transposable and B <= 64: PA_KERNEL_TILE_WIDE with word_bytes W = the
+ *    largest power of two <= 16 dividing B and both base addresses, and
+ *    words_per_element m = B / W;
+ *  - otherwise: LINEAR over the descriptor expanded to W-byte words (an
+ *    inner axis of m words), byteified = 0.
+ * words_per_element is 1 wherever the kernel does not split elements. */
+pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int64_t scalar_size, int64_t ncomp,
+                                   const void *src, const void *dst,
+                                   int64_t out[5]);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@
  *  - every data movement (pack, unpack, fused local/self copy) is a strided
  *    copy descriptor executed by one of three HIP kernels chosen at plan
  *    time: a vector 1-D copy, a batched linear-runs copy, or an LDS-tiled
- *    N-d transpose (coalesced reads AND writes, 64-wide wavefronts);
+ *    N-d transpose (coalesced reads AND writes, 64-wide wavefronts; packed
+ *    and wide-element variants for 1-/2-byte and composite elements);
  *  - the subgroup exchange is grouped ncclSend/ncclRecv (RCCL over xGMI) on
  *    the caller's HIP stream — replacing MPI.Isend/Irecv / MPI.Alltoallv!
  *    (Transpositions.jl:419-428, 463-479);
@@ -444,6 +445,86 @@ __global__ __launch_bounds__(NTHR) void k_transpose_tile_pk(
     }
 }
 
+/* LDS-tiled transpose for WIDE elements: an element is m words of WordT
+ * (components fastest), e.g. 3 x f64 = three 8-B words.  The descriptor is
+ * in ELEMENT units; the tile is ti x tj elements (runtime, chosen per
+ * element size by wide_tile_shape()).
+ *
+ * Load: each tile row along ta is ni*m contiguous src words; lanes sweep the
+ * word index q and write LDS word j*pitch + q (consecutive, conflict-free).
+ * Store: each tile row along axis 0 is nj*m contiguous dst words; lane q
+ * writes word q%m of element j = q/m, read from LDS word
+ * j*pitch + i*m + q%m = q + j*(pitch-m) + i*m.  The host picks
+ * pitch == m (mod 256/sizeof(WordT)), so consecutive lanes read consecutive
+ * LDS words modulo the 256-B bank span: no bank conflicts in either phase.
+ *
+ * M > 0 is the compile-time words-per-element (M = 3: vectors of three, the
+ * common case — q/3 is a constant multiply); M == 0 takes m at runtime and
+ * divides with the host-computed magic = ceil(2^32/m), exact for q < 2^26. */
+template <typename WordT, int M>
+__global__ __launch_bounds__(256) void k_transpose_tile_wide(
+    const WordT *__restrict__ src, WordT *__restrict__ dst, DescDev d, int ta,
+    int m_rt, uint32_t magic, int ti, int tj, int pitch, int64_t ntile_i,
+    int64_t ntile_j, int64_t nblocks)
+{
+    extern __shared__ uint4 wide_lds[];
+    WordT *tile = (WordT *)wide_lds;
+    constexpr int NR = 4;
+
+    const int tx = threadIdx.x; /* 0..63 */
+    const int ty = threadIdx.y; /* 0..NR-1 */
+    const int m = M > 0 ? M : m_rt;
+
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int64_t t_i = bid % ntile_i;
+    int64_t rest = bid / ntile_i;
+    const int64_t t_j = rest % ntile_j;
+    int64_t batch = rest / ntile_j;
+
+    int64_t so_b = d.soff, do_b = d.doff;
+    for (int a = 1; a < d.nd; a++) {
+        if (a == ta) continue;
+        const int64_t j = batch % d.dims[a];
+        batch /= d.dims[a];
+        so_b += j * d.sstr[a];
+        do_b += j * d.dstr[a];
+    }
+
+    const int64_t i0 = t_i * ti;
+    const int ni = (int)(d.dims[0] - i0 < ti ? d.dims[0] - i0 : ti);
+    const int64_t j0 = t_j * tj;
+    const int nj = (int)(d.dims[ta] - j0 < tj ? d.dims[ta] - j0 : tj);
+
+    /* load: lanes sweep the words of one src row, rows sweep ta */
+    {
+        const int64_t sj = d.sstr[ta];
+        const WordT *base = src + (so_b + i0 + j0 * sj) * m;
+        const int nw = ni * m;
+        for (int j = ty; j < nj; j += NR) {
+            const WordT *row = base + (int64_t)j * sj * m;
+            WordT *trow = tile + j * pitch;
+            for (int q = tx; q < nw; q += 64) trow[q] = row[q];
+        }
+    }
+    __syncthreads();
+    /* store: lanes sweep the words of one dst row, rows sweep axis 0 */
+    {
+        const int64_t di = d.dstr[0];
+        WordT *base = dst + (do_b + j0 + i0 * di) * m;
+        const int nw = nj * m;
+        const int skip = pitch - m;
+        for (int i = ty; i < ni; i += NR) {
+            WordT *row = base + (int64_t)i * di * m;
+            const WordT *tcol = tile + i * m;
+            for (int q = tx; q < nw; q += 64) {
+                const int j = M > 0 ? q / M : (int)__umulhi((uint32_t)q, magic);
+                row[q] = tcol[q + j * skip];
+            }
+        }
+    }
+}
+
 /* ================= descriptor normalization & dispatch ============= */
 
 struct CopyDescH {
@@ -562,7 +643,11 @@ struct KernelSel {
     int byteified = 0; /* went through the byte-ify fallback */
     int sweep = 1;     /* j-tiles swept per workgroup (tile kernels) */
     int ta = -1;       /* dst-contiguous axis (tile kernels) */
-    CopyDescH d;       /* the descriptor the kernel runs, in `word` units */
+    int m = 1;         /* words per element (wide tile / word-expanded) */
+    int ti = 0, tj = 0, pitch = 0; /* wide tile: shape (elements), LDS row
+                                    * pitch (words) */
+    CopyDescH d;       /* the descriptor the kernel runs, in `word` units
+                        * (wide tile: in ELEMENT units of m words each) */
 };
 
 /* sweep depth of the 4-/8-byte tiles: long sweeps win on tall-skinny shapes
@@ -688,6 +773,162 @@ static pa_status select_kernel(const CopyDescH &dn, int64_t esz,
     }
 }
 
+/* ---- composite elements: ncomp scalars of ssz bytes, components fastest */
+
+/* Tile shape (elements) of the wide tile per element size B: 16 rows along
+ * ta, and along axis 0 the largest power of two (16..256) whose row is at
+ * most 1536 bytes — a ~24 KiB tile, six or more workgroups per CU.
+ * Probe-measured on MI355X at the 512^3 permuted shape over ti in 16..256
+ * and tj in 8..64 for B = 6, 12, 24, 48 (composite elements):
+ * the best or within 2% of the best shape for each B; square 32x32 / 64x64
+ * tiles were 15-45% slower. */
+static void wide_tile_shape(int64_t B, int *ti, int *tj)
+{
+    int t = 256;
+    while (t > 16 && t * B > 1536) t >>= 1;
+    *ti = t;
+    *tj = 16;
+}
+
+#define PA_WIDE_MAX_BYTES 64
+
+/* the (scalar_size, ncomp) pairs the engine accepts: any positive size for
+ * one scalar per element, a power of two <= 16 for composite elements */
+static pa_status check_comp(int64_t scalar_size, int64_t ncomp)
+{
+    if (ncomp < 1) return fail("invalid ncomp %lld", (long long)ncomp);
+    if (scalar_size <= 0) return fail("invalid elem_size");
+    if (ncomp > 1 && !(scalar_size == 1 || scalar_size == 2 ||
+                       scalar_size == 4 || scalar_size == 8 ||
+                       scalar_size == 16))
+        return fail("invalid scalar_size %lld for ncomp %lld: must be 1, 2, "
+                    "4, 8 or 16", (long long)scalar_size, (long long)ncomp);
+    return 0;
+}
+
+static pa_status select_kernel_comp(const CopyDescH &dn, int64_t ssz,
+                                    int64_t ncomp, const void *src,
+                                    const void *dst, KernelSel *out)
+{
+    if (pa_status cst = check_comp(ssz, ncomp)) return cst;
+    /* one scalar per element: exactly the plain elem_size decision */
+    if (ncomp == 1) return select_kernel(dn, ssz, src, dst, out);
+    const int64_t B = ssz * ncomp;
+    /* power-of-two totals (2 x f32, 2 x f64, 4 x f16): the tuned tiles */
+    if (B == 1 || B == 2 || B == 4 || B == 8 || B == 16)
+        return select_kernel(dn, B, src, dst, out);
+
+    *out = KernelSel();
+    if (dn.total == 0) return 0;
+    const uintptr_t ptrs = (uintptr_t)src | (uintptr_t)dst;
+
+    if (dn.sstr[0] == 1 && dn.dstr[0] == 1) {
+        /* linear at element level: widest word dividing the run, every
+         * stride/offset in bytes, and both base addresses */
+        CopyDescH w;
+        int64_t W = 0;
+        for (int64_t cand : {16, 8, 4, 2, 1})
+            if ((ptrs & (uintptr_t)(cand - 1)) == 0 &&
+                word_scale(dn, B, cand, &w)) { W = cand; break; }
+        if (!W) return fail("word_scale(1)");
+        out->word = (int)W;
+        out->d = w;
+        if (w.nd == 1)
+            out->kind = (W == 16 && w.total * 16 >= (512ll << 20))
+                            ? PA_KERNEL_COPY_1D_NT
+                            : PA_KERNEL_COPY_1D;
+        else
+            out->kind = PA_KERNEL_LINEAR;
+        return 0;
+    }
+
+    /* every offset and stride is a whole number of elements, so only the
+     * base pointers can lower the word below the largest power of two
+     * dividing B */
+    int64_t W = 16;
+    while (W > 1 && (B % W || (ptrs & (uintptr_t)(W - 1)))) W >>= 1;
+    const int64_t m = B / W;
+
+    int ta = -1;
+    if (dn.sstr[0] == 1)
+        for (int a = 1; a < dn.nd; a++)
+            if (dn.dstr[a] == 1) { ta = a; break; }
+
+    if (ta > 0 && B <= PA_WIDE_MAX_BYTES) {
+        out->kind = PA_KERNEL_TILE_WIDE;
+        out->word = (int)W;
+        out->m = (int)m;
+        out->ta = ta;
+        out->d = dn;
+        wide_tile_shape(B, &out->ti, &out->tj);
+        /* LDS row pitch in words: >= ti*m and == m modulo the 256-B bank
+         * span, so the store phase's m-word runs land on consecutive
+         * banks across the row jump */
+        const int64_t span = 256 / W;
+        out->pitch =
+            (int)(m + ((int64_t)(out->ti - 1) * m + span - 1) / span * span);
+        return 0;
+    }
+
+    /* no contiguous axis, or an element past the wide-tile cap: expand to
+     * words (an inner axis of m unit-stride words) and run the linear
+     * kernel — correct and slow */
+    {
+        if (dn.nd + 1 > MAXND) return fail("too many dims to word-expand");
+        int64_t dims[MAXND + 1], ss[MAXND + 1], ds[MAXND + 1];
+        dims[0] = m;
+        ss[0] = 1;
+        ds[0] = 1;
+        for (int a = 0; a < dn.nd; a++) {
+            dims[a + 1] = dn.dims[a];
+            ss[a + 1] = dn.sstr[a] * m;
+            ds[a + 1] = dn.dstr[a] * m;
+        }
+        out->d = normalize_desc(dn.nd + 1, dims, ss, dn.soff * m, ds,
+                                dn.doff * m);
+        if (out->d.sstr[0] != 1 || out->d.dstr[0] != 1)
+            return fail("word expansion lost its unit axis");
+        out->kind = out->d.nd == 1 ? PA_KERNEL_COPY_1D : PA_KERNEL_LINEAR;
+        out->word = (int)W;
+        out->m = (int)m;
+        return 0;
+    }
+}
+
+template <typename WordT>
+static pa_status launch_tile_wide(const KernelSel &k, const char *s, char *d,
+                                  hipStream_t stream)
+{
+    const CopyDescH &dn = k.d;
+    const int ta = k.ta;
+    if (k.m < 2 || k.ti < 1 || k.tj < 1 || k.pitch < k.ti * k.m)
+        return fail("bad wide-tile selection");
+    DescDev dd = to_dev(dn);
+    int64_t nbatch = 1;
+    for (int a = 1; a < dn.nd; a++)
+        if (a != ta) nbatch *= dn.dims[a];
+    const int64_t nti = (dn.dims[0] + k.ti - 1) / k.ti;
+    const int64_t ntj = (dn.dims[ta] + k.tj - 1) / k.tj;
+    const int64_t nblocks = nti * ntj * nbatch;
+    dim3 grid;
+    pa_status gst = grid2d(nblocks, 256, &grid);
+    if (gst) return gst;
+    const size_t lds = (size_t)k.tj * k.pitch * sizeof(WordT);
+    if (lds > (64u << 10)) return fail("wide tile needs %zu B of LDS", lds);
+    const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + k.m - 1) / k.m);
+    if (k.m == 3)
+        hipLaunchKernelGGL((k_transpose_tile_wide<WordT, 3>), grid,
+                           dim3(64, 4), lds, stream, (const WordT *)s,
+                           (WordT *)d, dd, ta, k.m, magic, k.ti, k.tj,
+                           k.pitch, nti, ntj, nblocks);
+    else
+        hipLaunchKernelGGL((k_transpose_tile_wide<WordT, 0>), grid,
+                           dim3(64, 4), lds, stream, (const WordT *)s,
+                           (WordT *)d, dd, ta, k.m, magic, k.ti, k.tj,
+                           k.pitch, nti, ntj, nblocks);
+    return 0;
+}
+
 template <typename T>
 static pa_status launch_tile(const KernelSel &k, const char *s, char *d,
                              hipStream_t stream)
@@ -782,6 +1023,11 @@ static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
                                dim3(256), 0, stream,
                                (const uint32_t *)s + w.soff,
                                (uint32_t *)d + w.doff, w.total);
+        else if (W == 2)
+            hipLaunchKernelGGL(k_copy_1d<uint16_t>, blocks,
+                               dim3(256), 0, stream,
+                               (const uint16_t *)s + w.soff,
+                               (uint16_t *)d + w.doff, w.total);
         else
             hipLaunchKernelGGL(k_copy_1d<uint8_t>, blocks, dim3(256),
                                0, stream, (const uint8_t *)s + w.soff,
@@ -805,6 +1051,10 @@ static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
             hipLaunchKernelGGL(k_copy_linear<uint32_t>, blocks,
                                dim3(256), 0, stream, (const uint32_t *)s,
                                (uint32_t *)d, dd);
+        else if (W == 2)
+            hipLaunchKernelGGL(k_copy_linear<uint16_t>, blocks,
+                               dim3(256), 0, stream, (const uint16_t *)s,
+                               (uint16_t *)d, dd);
         else
             hipLaunchKernelGGL(k_copy_linear<uint8_t>, blocks,
                                dim3(256), 0, stream, (const uint8_t *)s,
@@ -871,6 +1121,14 @@ static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
                     : launch_tile_pk<uint8_t>(k, s, d, stream);
         if (st) return st;
         break;
+    case PA_KERNEL_TILE_WIDE:
+        st = W == 16  ? launch_tile_wide<uint4>(k, s, d, stream)
+             : W == 8 ? launch_tile_wide<uint64_t>(k, s, d, stream)
+             : W == 4 ? launch_tile_wide<uint32_t>(k, s, d, stream)
+             : W == 2 ? launch_tile_wide<uint16_t>(k, s, d, stream)
+                      : launch_tile_wide<uint8_t>(k, s, d, stream);
+        if (st) return st;
+        break;
     case PA_KERNEL_GENERIC: {
         DescDev dd = to_dev(w);
         const dim3 blocks(grid_for(w.total, 256)); /* grid-stride kernel */
@@ -902,11 +1160,11 @@ static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
     return 0;
 }
 
-static pa_status launch_desc(const CopyDescH &dn, int64_t esz,
+static pa_status launch_desc(const CopyDescH &dn, int64_t ssz, int64_t ncomp,
                              const void *src, void *dst, hipStream_t stream)
 {
     KernelSel k;
-    pa_status st = select_kernel(dn, esz, src, dst, &k);
+    pa_status st = select_kernel_comp(dn, ssz, ncomp, src, dst, &k);
     if (st) return st;
     return launch_sel(k, src, dst, stream);
 }
@@ -1013,7 +1271,9 @@ struct pa_plan {
     int rank;
     int E;
     std::vector<int64_t> extra;
-    int64_t esz;
+    int64_t esz;   /* bytes per element = ssz * ncomp */
+    int64_t ssz;   /* bytes per scalar */
+    int64_t ncomp; /* scalars per element, components fastest */
     int R;    /* -1 = same decomposition */
     int P;    /* subgroup size */
     int myk;  /* my coordinate along R */
@@ -1394,6 +1654,15 @@ pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
                          int64_t elem_size, int e, const int64_t *extra_dims,
                          int rank, int flags, pa_plan **out)
 {
+    return pa_plan_create_comp(pin, pout, elem_size, 1, e, extra_dims, rank,
+                               flags, out);
+}
+
+pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
+                              int64_t scalar_size, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              pa_plan **out)
+{
     /* assert_compatible (Transpositions.jl:182-199) */
     if (pin->topo.m != pout->topo.m || pin->topo.dims != pout->topo.dims)
         return fail("pencil topologies must be the same.");
@@ -1410,7 +1679,7 @@ pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
         return fail("pencil decompositions must differ in at most one "
                     "dimension.");
     if (rank < 0 || rank >= pin->topo.nranks) return fail("rank out of range");
-    if (elem_size <= 0) return fail("invalid elem_size");
+    if (pa_status cst = check_comp(scalar_size, ncomp)) return cst;
     if (pin->n + e > MAXND)
         return fail("too many dims: N+E must be <= %d", MAXND);
 
@@ -1420,7 +1689,9 @@ pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
     pl->rank = rank;
     pl->E = e;
     if (e) pl->extra.assign(extra_dims, extra_dims + e);
-    pl->esz = elem_size;
+    pl->esz = scalar_size * ncomp;
+    pl->ssz = scalar_size;
+    pl->ncomp = ncomp;
     pl->R = R;
     pl->aliased = (flags & 1) != 0;
     if (const char *ce = getenv("PENCILHIP_EXCHANGE_CHUNKS")) {
@@ -1653,12 +1924,13 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
     for (auto &blk : p->peers)
         if (blk.has_pack) {
             pa_status st =
-                launch_desc(blk.pack, p->esz, src_parent, p->send_buf, stream);
+                launch_desc(blk.pack, p->ssz, p->ncomp, src_parent,
+                            p->send_buf, stream);
             if (st) return st;
         }
     if (p->has_self) {
-        pa_status st = launch_desc(p->self_pack, p->esz, src_parent,
-                                   p->recv_buf, stream);
+        pa_status st = launch_desc(p->self_pack, p->ssz, p->ncomp,
+                                   src_parent, p->recv_buf, stream);
         if (st) return st;
     }
     TM_REC(1, stream);
@@ -1739,12 +2011,13 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
      * exchange (aliased mode: unpack the staged self block instead) */
     if (p->has_local) {
         pa_status st =
-            launch_desc(p->local, p->esz, src_parent, dst_parent, stream);
+            launch_desc(p->local, p->ssz, p->ncomp, src_parent, dst_parent,
+                        stream);
         if (st) return st;
     }
     if (p->has_self) {
-        pa_status st = launch_desc(p->self_unpack, p->esz, p->recv_buf,
-                                   dst_parent, stream);
+        pa_status st = launch_desc(p->self_unpack, p->ssz, p->ncomp,
+                                   p->recv_buf, dst_parent, stream);
         if (st) return st;
     }
     TM_REC(2, stream);
@@ -1758,8 +2031,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
         TM_REC(5, stream);
         for (auto &blk : p->peers)
             if (blk.has_unpack) {
-                pa_status st = launch_desc(blk.unpack, p->esz, p->recv_buf,
-                                           dst_parent, stream);
+                pa_status st =
+                    launch_desc(blk.unpack, p->ssz, p->ncomp, p->recv_buf,
+                                dst_parent, stream);
                 if (st) return st;
             }
         TM_REC(6, stream);
@@ -1774,7 +2048,8 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
                 if (hi <= lo) continue;
                 CopyDescH d = chunk_of_raw(blk.unpack_raw, lo, hi);
                 pa_status st =
-                    launch_desc(d, p->esz, p->recv_buf, dst_parent, stream);
+                    launch_desc(d, p->ssz, p->ncomp, p->recv_buf, dst_parent,
+                                stream);
                 if (st) return st;
             }
         }
@@ -1909,9 +2184,19 @@ pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
                          int64_t elem_size, const void *src, void *dst,
                          void *stream)
 {
+    return pa_device_copy_comp(nd, dims, sstr, soff, dstr, doff, elem_size, 1,
+                               src, dst, stream);
+}
+
+pa_status pa_device_copy_comp(int nd, const int64_t *dims,
+                              const int64_t *sstr, int64_t soff,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp,
+                              const void *src, void *dst, void *stream)
+{
     if (nd <= 0 || nd > MAXND) return fail("bad nd");
     CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
-    return launch_desc(d, elem_size, src, dst, (hipStream_t)stream);
+    return launch_desc(d, scalar_size, ncomp, src, dst, (hipStream_t)stream);
 }
 
 pa_status pa_copy_kernel_kind(int nd, const int64_t *dims, const int64_t *sstr,
@@ -1919,16 +2204,32 @@ pa_status pa_copy_kernel_kind(int nd, const int64_t *dims, const int64_t *sstr,
                               int64_t elem_size, const void *src,
                               const void *dst, int64_t out[4])
 {
+    int64_t o5[5];
+    pa_status st = pa_copy_kernel_kind_comp(nd, dims, sstr, soff, dstr, doff,
+                                            elem_size, 1, src, dst, o5);
+    if (st) return st;
+    for (int i = 0; i < 4; i++) out[i] = o5[i];
+    return 0;
+}
+
+pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int64_t scalar_size, int64_t ncomp,
+                                   const void *src, const void *dst,
+                                   int64_t out[5])
+{
     if (nd <= 0 || nd > MAXND) return fail("bad nd");
-    if (elem_size <= 0) return fail("bad elem_size");
+    if (scalar_size <= 0) return fail("bad elem_size");
     CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
     KernelSel k;
-    pa_status st = select_kernel(d, elem_size, src, dst, &k);
+    pa_status st = select_kernel_comp(d, scalar_size, ncomp, src, dst, &k);
     if (st) return st;
     out[0] = k.kind;
     out[1] = k.word;
     out[2] = k.byteified;
     out[3] = k.sweep;
+    out[4] = k.m;
     return 0;
 }
 

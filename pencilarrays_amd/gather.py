@@ -33,13 +33,15 @@ def _logical_block(x: PencilArray) -> np.ndarray:
 
 
 def gather_sim(arrays: Sequence[PencilArray]) -> np.ndarray:
-    """Global logical-order array from all ranks' PencilArrays.  Torch data
+    """Global logical-order array from all ranks' PencilArrays, of shape
+    ``elem_dims + size_global + extra_dims``.  Torch data
     of a dtype numpy cannot represent (``torch.bfloat16``) comes back as the
     same-width unsigned-integer bit pattern (``uint16``), placed exactly as
     ``int16`` data would be."""
     p0 = arrays[0].pencil
     extra = arrays[0].extra_dims
-    shape = tuple(p0.size_global) + extra
+    elem = arrays[0].elem_dims
+    shape = elem + tuple(p0.size_global) + extra
     first = arrays[0].data
     dtype = first.dtype if isinstance(first, np.ndarray) else \
         bits_dtype(first.dtype)
@@ -47,7 +49,8 @@ def gather_sim(arrays: Sequence[PencilArray]) -> np.ndarray:
     for r, x in enumerate(arrays):
         assert x.rank == r
         region = x.pencil.axes_for_rank(r)
-        sl = tuple(slice(lo, hi) for lo, hi in region) + \
+        sl = tuple(slice(None) for _ in elem) + \
+            tuple(slice(lo, hi) for lo, hi in region) + \
             tuple(slice(None) for _ in extra)
         dest[sl] = _logical_block(x)
     return dest
@@ -72,17 +75,19 @@ def gather_dist(x: PencilArray, root: int = 0) -> Optional[np.ndarray]:
 
     p = x.pencil
     extra = x.extra_dims
-    shape = tuple(p.size_global) + extra
+    elem = x.elem_dims
+    shape = elem + tuple(p.size_global) + extra
     dest = np.empty(shape, dtype=out_dtype)
     topo = p.topology
     for r in range(topo.nranks):
         region = p.axes_for_rank(r)
-        sl = tuple(slice(lo, hi) for lo, hi in region) + \
+        sl = tuple(slice(None) for _ in elem) + \
+            tuple(slice(lo, hi) for lo, hi in region) + \
             tuple(slice(None) for _ in extra)
         if r == root:
             dest[sl] = block.view(out_dtype)
         else:
-            dims = tuple(hi - lo for lo, hi in region) + extra
+            dims = elem + tuple(hi - lo for lo, hi in region) + extra
             buf = torch.empty(dims, dtype=torch.from_numpy(block).dtype)
             dist.recv(buf, src=r, tag=MPI_TAG)
             dest[sl] = buf.numpy().view(out_dtype)

@@ -19,11 +19,14 @@ from .pencil import Pencil
 class ManyPencilArray:
     def __init__(self, pencils: Sequence[Pencil], rank: int,
                  dtype="float64", extra_dims: Tuple[int, ...] = (),
-                 backend: Optional[str] = None, device=None):
+                 backend: Optional[str] = None, device=None,
+                 elem_dims: Tuple[int, ...] = ()):
         if backend is None:  # a device implies torch storage
             backend = "numpy" if device is None else "torch"
         extra_dims = tuple(int(e) for e in extra_dims)
-        pex = math.prod(extra_dims) if extra_dims else 1
+        elem_dims = tuple(int(c) for c in elem_dims)
+        # flat lengths in scalars: elem_dims components per element
+        pex = math.prod(extra_dims) * math.prod(elem_dims)
         lengths = [p.length_local(rank) * pex for p in pencils]
         n = max(lengths) if lengths else 0
         if backend == "numpy":
@@ -37,7 +40,7 @@ class ManyPencilArray:
         self.data = flat
         self.pencils = tuple(pencils)
         self.arrays = tuple(
-            PencilArray(p, rank, flat[:ln], extra_dims)
+            PencilArray(p, rank, flat[:ln], extra_dims, elem_dims)
             for p, ln in zip(pencils, lengths))
 
     @property

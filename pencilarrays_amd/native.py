@@ -62,11 +62,13 @@ KERNEL_TILE = 4
 KERNEL_TILE_VS = 5
 KERNEL_TILE_PK = 6
 KERNEL_GENERIC = 7
+KERNEL_TILE_WIDE = 8
 KERNEL_NAMES = {
     KERNEL_NONE: "NONE", KERNEL_COPY_1D: "COPY_1D",
     KERNEL_COPY_1D_NT: "COPY_1D_NT", KERNEL_LINEAR: "LINEAR",
     KERNEL_TILE: "TILE", KERNEL_TILE_VS: "TILE_VS",
     KERNEL_TILE_PK: "TILE_PK", KERNEL_GENERIC: "GENERIC",
+    KERNEL_TILE_WIDE: "TILE_WIDE",
 }
 
 
@@ -75,16 +77,35 @@ class KernelKind(NamedTuple):
     word_bytes: int
     byteified: int
     sweep_depth: int
+    words_per_element: int = 1
+
+
+def _desc_fields(desc):
+    if hasattr(desc, "sstrides"):
+        return (desc.dims, desc.sstrides, desc.soffset, desc.dstrides,
+                desc.doffset)
+    return desc
 
 
 def copy_kernel_kind(desc, esz: int, src_ptr: int = 0,
-                     dst_ptr: int = 0) -> KernelKind:
+                     dst_ptr: int = 0, ncomp: int = 1) -> KernelKind:
     """Which kernel ``pa_device_copy`` / a plan launches for ``desc`` with
     ``esz``-byte elements (host-only, no GPU needed).  ``desc`` is a
     ``plan.CopyDesc`` or the ``(dims, sstr, soff, dstr, doff)`` tuple of
     ``NativePlan.copydesc``.  The pointers are used for their alignment
-    only and never dereferenced."""
+    only and never dereferenced.  With ``ncomp > 1`` an element is ``ncomp``
+    scalars of ``esz`` bytes, components fastest (pa_copy_kernel_kind_comp);
+    ``words_per_element`` is then the fifth field of that query."""
     lib = load()
+    if ncomp != 1:
+        dims, sstr, soff, dstr, doff = _desc_fields(desc)
+        nd = len(dims)
+        out = (I64 * 5)()
+        _check(lib, lib.pa_copy_kernel_kind_comp(
+            nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+            (I64 * nd)(*dstr), I64(doff), I64(esz), I64(ncomp), VP(src_ptr),
+            VP(dst_ptr), out), "pa_copy_kernel_kind_comp")
+        return KernelKind(*(int(v) for v in out))
     if hasattr(desc, "sstrides"):
         dims, sstr, soff, dstr, doff = (desc.dims, desc.sstrides,
                                         desc.soffset, desc.dstrides,
@@ -100,12 +121,32 @@ def copy_kernel_kind(desc, esz: int, src_ptr: int = 0,
     return KernelKind(*(int(v) for v in out))
 
 
+def device_copy(desc, esz: int, src_ptr: int, dst_ptr: int,
+                stream: int = 0, ncomp: int = 1) -> None:
+    """Run one strided-copy descriptor on the device (pa_device_copy /
+    pa_device_copy_comp): elements of ``ncomp`` scalars of ``esz`` bytes."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    args = (nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+            (I64 * nd)(*dstr), I64(doff), I64(esz))
+    tail = (VP(src_ptr), VP(dst_ptr), VP(stream))
+    if ncomp == 1:
+        _check(lib, lib.pa_device_copy(*args, *tail), "pa_device_copy")
+    else:
+        _check(lib, lib.pa_device_copy_comp(*args, I64(ncomp), *tail),
+               "pa_device_copy_comp")
+
+
 class NativePlan:
     """pa_plan plus the pa_topology/pa_pencil handles it needs.  Plan
     building is host-only (works without a GPU); execute needs one."""
 
     def __init__(self, Pi, Po, rank: int, elem_size: int,
-                 extra_dims: Tuple[int, ...] = (), aliased: bool = False):
+                 extra_dims: Tuple[int, ...] = (), aliased: bool = False,
+                 ncomp: int = 1):
+        """``ncomp > 1``: elements of ``ncomp`` scalars of ``elem_size``
+        bytes, components fastest (pa_plan_create_comp)."""
         lib = self.lib = load()
         topo = Pi.topology
         # both pa_pencils are built against ONE pa_topology handle, so the
@@ -133,11 +174,12 @@ class NativePlan:
         self._po = mk_pencil(Po)
         self._plan = VP()
         e = len(extra_dims)
-        _check(lib, lib.pa_plan_create(
-            self._pi, self._po, I64(elem_size), e,
+        self.ncomp = int(ncomp)
+        _check(lib, lib.pa_plan_create_comp(
+            self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
             (I64 * e)(*extra_dims) if e else None, rank,
             1 if aliased else 0,
-            ctypes.byref(self._plan)), "pa_plan_create")
+            ctypes.byref(self._plan)), "pa_plan_create_comp")
         self.nproc_sub = lib.pa_plan_nproc_sub(self._plan)
         self.r_dim = lib.pa_plan_r_dim(self._plan)
         self.my_k = lib.pa_plan_my_k(self._plan)
@@ -398,7 +440,8 @@ class NativeTransposition:
         esz = src.data.element_size()
         self.np_plan = plan
         self.native = NativePlan(plan.Pi, plan.Po, plan.rank, esz,
-                                 plan.extra_dims, aliased=plan.aliased)
+                                 plan.extra_dims, aliased=plan.aliased,
+                                 ncomp=src.ncomp)
         sb, rb = self.native.buffer_sizes()
         dev = src.data.device
         # Staging comes from the per-device shared pool (the reference's

@@ -57,6 +57,16 @@ def _unsupported(name: str) -> TypeError:
         f"{sorted(_JULIA_TYPES)})")
 
 
+def _reject_elem_dims(x) -> None:
+    """The on-disk metadata describes scalar element types only: it has no
+    place for vector-valued elements, so such arrays are refused."""
+    if getattr(x, "elem_dims", ()):
+        raise NotImplementedError(
+            f"pencilio does not support arrays with elem_dims "
+            f"(got elem_dims={x.elem_dims}): the file metadata cannot "
+            f"describe vector-valued elements")
+
+
 def _julia_type(dtype: np.dtype) -> str:
     try:
         return _JULIA_TYPES[dtype.name]
@@ -131,6 +141,7 @@ class MPIIOFile:
 
     def write(self, name: str, x: PencilArray, chunks: bool = False):
         """setindex!(file, x, name; chunks) (mpi_io.jl:172-189)."""
+        _reject_elem_dims(x)
         p = x.pencil
         offset = self.position
         dtype = _data_dtype(x.data)
@@ -205,6 +216,7 @@ class MPIIOFile:
     def read(self, name: str, x: PencilArray):
         """read!(file, x, name) (mpi_io.jl:232-263): checks element type,
         memory dims, byte size and endianness (check_metadata :293-325)."""
+        _reject_elem_dims(x)
         meta = self.meta["datasets"].get(name)
         if meta is None:
             raise KeyError(f"dataset '{name}' not found")
@@ -240,6 +252,7 @@ class MPIIOFile:
 
     def read_raw(self, x: PencilArray, offset: int = 0):
         """read!(file, x; offset) without metadata (mpi_io.jl:265-278)."""
+        _reject_elem_dims(x)
         dtype = _data_dtype(x.data)
         self._read_at(x, offset, False, np.dtype(dtype))
         return x

@@ -32,6 +32,15 @@ from .plan import TransposePlan, build_plan
 MPI_TAG = 42  # Transpositions.jl:469
 
 
+def _wire(buf: np.ndarray):
+    """A staging-buffer slice as a torch tensor for isend/irecv; opaque
+    (void) elements travel as their bytes."""
+    import torch
+    if buf.dtype.kind == "V":
+        buf = buf.view(np.uint8)
+    return torch.from_numpy(buf)
+
+
 def _arrays_alias(a, b) -> bool:
     """Base.mightalias equivalent (Transpositions.jl:250): do the two parent
     buffers share memory?  (ManyPencilArray in-place transposes.)"""
@@ -67,6 +76,10 @@ class Transposition:
             raise ValueError(
                 f"incompatible number of extra dimensions of PencilArrays: "
                 f"{src.extra_dims} != {dest.extra_dims}")
+        if dest.elem_dims != src.elem_dims:
+            raise ValueError(
+                f"incompatible element dimensions of PencilArrays: "
+                f"{src.elem_dims} != {dest.elem_dims}")
         if dest.rank != src.rank:
             raise ValueError("dest and src must live on the same rank")
         if method not in ("grouped", "point_to_point", "alltoallv"):
@@ -86,9 +99,10 @@ class Transposition:
 
     def _execute_numpy(self, use_dist: bool):
         plan = self.plan
-        src_flat = self.src.data
-        dst_flat = self.dest.data
-        itemsize = src_flat.itemsize
+        # vector-valued elements: one opaque B-byte item per element, so the
+        # element-unit descriptors apply unchanged
+        src_flat = self.src.element_view()
+        dst_flat = self.dest.element_view()
 
         if plan.r_dim is None or plan.nproc_sub == 1:
             if plan.local is not None:
@@ -138,11 +152,11 @@ class Transposition:
             if blk.peer_k == plan.my_k:
                 continue
             if blk.recv_nelem > 0:
-                rt = torch.from_numpy(
+                rt = _wire(
                     recv_buf[blk.recv_offset:blk.recv_offset + blk.recv_nelem])
                 reqs.append(dist.irecv(rt, src=blk.global_rank, tag=MPI_TAG))
             if blk.send_nelem > 0:
-                st = torch.from_numpy(
+                st = _wire(
                     send_buf[blk.send_offset:blk.send_offset + blk.send_nelem])
                 reqs.append(dist.isend(st, dst=blk.global_rank, tag=MPI_TAG))
 
@@ -218,24 +232,31 @@ def run_transpose_sim(dests: Sequence[PencilArray],
     plans = [build_plan(s.pencil, d.pencil, r, s.extra_dims,
                         aliased=_arrays_alias(s.data, d.data))
              for r, (d, s) in enumerate(zip(dests, srcs))]
+    for d, s in zip(dests, srcs):
+        if d.elem_dims != s.elem_dims:
+            raise ValueError(
+                f"incompatible element dimensions of PencilArrays: "
+                f"{s.elem_dims} != {d.elem_dims}")
+    sflat = [s.element_view() for s in srcs]
+    dflat = [d.element_view() for d in dests]
 
-    send_bufs = [np.empty(p.send_nelem_total, dtype=srcs[r].data.dtype)
+    send_bufs = [np.empty(p.send_nelem_total, dtype=sflat[r].dtype)
                  for r, p in enumerate(plans)]
-    recv_bufs = [np.empty(p.recv_nelem_total, dtype=srcs[r].data.dtype)
+    recv_bufs = [np.empty(p.recv_nelem_total, dtype=sflat[r].dtype)
                  for r, p in enumerate(plans)]
 
     # pack on every rank (incl. staged self blocks, before any dst write)
     for r, p in enumerate(plans):
         for blk in p.peers:
             if blk.pack is not None:
-                apply_copy(blk.pack, srcs[r].data, send_bufs[r])
+                apply_copy(blk.pack, sflat[r], send_bufs[r])
         if p.self_pack is not None:
-            apply_copy(p.self_pack, srcs[r].data, recv_bufs[r])
+            apply_copy(p.self_pack, sflat[r], recv_bufs[r])
     for r, p in enumerate(plans):
         if p.local is not None:
-            apply_copy(p.local, srcs[r].data, dests[r].data)
+            apply_copy(p.local, sflat[r], dflat[r])
         elif p.self_unpack is not None:
-            apply_copy(p.self_unpack, recv_bufs[r], dests[r].data)
+            apply_copy(p.self_unpack, recv_bufs[r], dflat[r])
 
     # exchange: copy each send block into the receiver's recv buffer
     for r, p in enumerate(plans):
@@ -256,4 +277,4 @@ def run_transpose_sim(dests: Sequence[PencilArray],
     for r, p in enumerate(plans):
         for blk in p.peers:
             if blk.unpack is not None:
-                apply_copy(blk.unpack, recv_bufs[r], dests[r].data)
+                apply_copy(blk.unpack, recv_bufs[r], dflat[r])
