@@ -154,6 +154,103 @@ pa_status pa_plan_copydesc(const pa_plan *p, int which, int k, int64_t *nd,
                            int64_t *dims, int64_t *sstr, int64_t *soff,
                            int64_t *dstr, int64_t *doff);
 
+/* ---- multi-field transposes -------------------------------------------- */
+/* n separately allocated fields of ONE pencil pair in one call — what a host
+ * does today with n transpose! calls (Transpositions.jl:161-180; the
+ * reference batches only fields allocated together, extra_dims,
+ * arrays.jl:105-106).  One plan (element units, unchanged) serves any n:
+ *
+ *  - staging is n times the plan's sizes.  A staging block that starts at
+ *    element offset o with c elements in the single-field plan (a peer's
+ *    send block, a peer's recv block, the aliased self block in the recv
+ *    tail) holds field f at n*o + f*c; n = 1 is today's layout;
+ *  - peer k's message is the contiguous range [n*o_k, n*(o_k+c_k)): ONE send
+ *    and ONE recv per peer whatever n is (Transpositions.jl:419-428 posts
+ *    one per peer per field);
+ *  - each stage is one grouped kernel launch per kernel signature (kind,
+ *    word size) over a device-resident table of descriptors.  Selection per
+ *    descriptor is that of pa_copy_kernel_kind_comp.  COPY_1D/LINEAR, TILE
+ *    and TILE_VS at sweep depth 1 are grouped; any other selection runs as
+ *    an ordinary launch from the same stage call.
+ *
+ * Staging MUST come from pa_plan_set_buffers with at least
+ * pa_plan_buffer_sizes_many bytes (the hipMalloc fallback of
+ * pa_transpose_execute sizes for one field and is refused here).  Tables are
+ * cached per plan, keyed on n, the stage and every pointer involved; steady-
+ * state calls on the same arrays allocate nothing.  pa_plan_set_buffers
+ * drops the cache (and waits for the device). */
+
+/* send_buf/recv_buf sizes for n fields (Pencils.jl:187-189, times n). */
+pa_status pa_plan_buffer_sizes_many(const pa_plan *p, int n,
+                                    int64_t *send_bytes, int64_t *recv_bytes);
+/* The message exchanged with subgroup peer k for n fields, in BYTES into the
+ * staging buffers: out = {send_off, send_bytes, recv_off, recv_bytes} — the
+ * buffer ranges of MPI.Isend / MPI.Irecv! in Transpositions.jl:463-479.  All
+ * zero for k == my coordinate (the self block is never a message).  A host
+ * with its own transport (GPU-aware MPI) needs only this and the stages. */
+pa_status pa_plan_peer_message(const pa_plan *p, int n, int k, int64_t out[4]);
+
+/* The stages of transpose! separately, asynchronous on `stream`:
+ *   pack_many   = step 1 of pa_transpose_execute: every pack of every field
+ *                 into send_buf (transpose_send!, Transpositions.jl:346-431),
+ *                 and in aliased mode the staged self packs (:394-404);
+ *   local_many  = step 3: the fused local copies, or in aliased mode the
+ *                 staged self unpacks;
+ *   unpack_many = step 4: every unpack of every field from recv_buf
+ *                 (transpose_recv!, :489-536).
+ * ORDERING A FOREIGN EXCHANGE IS THE HOST'S JOB: the sends may start only
+ * once pack_many has completed on `stream` (synchronize it, or make the
+ * transport's stream wait on an event), and unpack_many may be enqueued only
+ * after every recv has landed in recv_buf.  local_many touches no remote
+ * block and may overlap the exchange.  In aliased mode enqueue pack_many
+ * before local_many and unpack_many: they write the destinations. */
+pa_status pa_transpose_pack_many(pa_plan *p, int n, const void *const *srcs,
+                                 void *stream);
+pa_status pa_transpose_local_many(pa_plan *p, int n, const void *const *srcs,
+                                  void *const *dsts, void *stream);
+pa_status pa_transpose_unpack_many(pa_plan *p, int n, void *const *dsts,
+                                   void *stream);
+
+/* transpose!(t) for n fields: pack_many -> ONE grouped RCCL exchange (one
+ * ncclSend/ncclRecv per peer at the pa_plan_peer_message ranges, on the
+ * engine's comm stream, event-ordered as in pa_transpose_execute) ->
+ * local_many -> unpack_many.  pa_transpose_wait and pa_plan_stage_times work
+ * after it unchanged.  PENCILHIP_EXCHANGE_CHUNKS does NOT apply: the
+ * exchange is always a single group.  PA_PLAN_ALIASED plans are supported
+ * (srcs and dsts may then alias in any combination): every pack and self
+ * pack of every field is enqueued before any write of a destination. */
+pa_status pa_transpose_execute_many(pa_plan *p, int n,
+                                    const void *const *srcs,
+                                    void *const *dsts, void *stream);
+
+/* Introspection (host-only, no GPU).  pa_plan_copydesc_many: the descriptor
+ * of field f of n, in the form and with the `which` of pa_plan_copydesc
+ * (0..4): the single-field descriptor with its staging-side offset moved by
+ * (n-1)*o + f*c. */
+pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
+                                int k, int64_t *nd, int64_t *dims,
+                                int64_t *sstr, int64_t *soff, int64_t *dstr,
+                                int64_t *doff);
+/* The launches a stage makes for these arrays (stage: 0 = pack, 1 = local,
+ * 2 = unpack), one row each: {kind, grouped 0/1, entries, workgroups}.  A
+ * grouped row of the linear family reports PA_KERNEL_LINEAR.  Pointers are
+ * used for alignment only and never dereferenced, like pa_copy_kernel_kind;
+ * srcs, dsts or single pointers may be NULL (taken as 256-byte aligned).
+ * Staging is taken from pa_plan_set_buffers, else assumed 256-byte aligned.
+ * At most max_rows rows are written; *nrows is the full count.  The stage
+ * calls execute exactly this list. */
+#define PA_STAGE_PACK   0
+#define PA_STAGE_LOCAL  1
+#define PA_STAGE_UNPACK 2
+pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
+                                 const void *const *srcs, void *const *dsts,
+                                 int max_rows, int64_t (*rows)[4], int *nrows);
+
+/* Stage tables this plan holds in its cache (at most 12, least recently used
+ * evicted): one per (n, stage, array set) that has run.  A repeated call on
+ * the same arrays leaves it unchanged — nothing was built or allocated. */
+int pa_plan_stage_table_count(const pa_plan *p);
+
 /* ---- reductions (src/reductions.jl:9-38) ----------------------------- */
 /* One ncclAllReduce over a communicator (normally the FULL topology comm):
  * the collective behind the reference's mapreduce/any/all.

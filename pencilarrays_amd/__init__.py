@@ -22,7 +22,14 @@ from .topology import Topology, dims_create
 from .pencil import Pencil
 from .array import PencilArray
 from .plan import CopyDesc, TransposePlan, build_plan, normalize_desc
-from .transpositions import Transposition, run_transpose_sim, transpose_into
+from .transpositions import (
+    MultiTransposition,
+    Transposition,
+    run_transpose_sim,
+    run_transpose_sim_many,
+    transpose_into,
+    transpose_many_into,
+)
 from .multiarrays import ManyPencilArray
 from .pencilio import MPIIOFile
 from . import reductions
@@ -35,6 +42,7 @@ gather = gather_dist
 __all__ = [
     "Topology", "dims_create", "Pencil", "PencilArray",
     "Transposition", "transpose_into", "run_transpose_sim", "ManyPencilArray",
+    "MultiTransposition", "transpose_many_into", "run_transpose_sim_many",
     "MPIIOFile", "reductions",
     "gather", "gather_sim", "gather_dist",
     "CopyDesc", "TransposePlan", "build_plan", "normalize_desc",

@@ -127,14 +127,15 @@ __global__ __launch_bounds__(256) void k_copy_1d_nt(
 
 /* Batched linear runs: axis 0 contiguous on both sides (coalesced); outer
  * axes strided.  Used for pack (strided window -> contiguous buffer when the
- * fastest axis survives) and its inverse.  Direct mapping (see k_copy_1d). */
+ * fastest axis survives) and its inverse.  Direct mapping (see k_copy_1d).
+ * The body is shared by k_copy_linear and the grouped k_group_linear: b is
+ * the (entry-local) flat block id. */
 template <typename T>
-__global__ __launch_bounds__(256) void k_copy_linear(const T *__restrict__ src,
-                                                     T *__restrict__ dst,
-                                                     DescDev d)
+__device__ __forceinline__ void linear_body(const T *__restrict__ src,
+                                            T *__restrict__ dst,
+                                            const DescDev &d, int64_t b)
 {
     const int64_t run = d.dims[0];
-    const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const int64_t idx = b * blockDim.x + threadIdx.x;
     if (idx >= d.total) return;
     int64_t o = idx / run;
@@ -147,6 +148,15 @@ __global__ __launch_bounds__(256) void k_copy_linear(const T *__restrict__ src,
         doo += j * d.dstr[a];
     }
     dst[doo] = src[so];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_copy_linear(const T *__restrict__ src,
+                                                     T *__restrict__ dst,
+                                                     DescDev d)
+{
+    linear_body<T>(src, dst, d,
+                   (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 /* Generic gather/scatter (rare fallback: no contiguous axis on either side
@@ -179,19 +189,20 @@ __global__ __launch_bounds__(256) void k_copy_generic(const T *__restrict__ src,
  * The unpack of a permuted pencil (copy_permuted!, Transpositions.jl:588-667)
  * is exactly this kernel; the reference's GPU path does a generic
  * permutedims! plus an extra temporary copy (:651-667 "TODO avoid
- * allocation") — here it is one kernel, no temporary. */
+ * allocation") — here it is one kernel, no temporary.
+ *
+ * The body is shared by k_transpose_tile and the grouped k_group_tile: bid
+ * is the (entry-local) flat block id, already checked against the block
+ * count. */
 template <typename T, int TILE_I, int TILE_J, int NROWS, int JCHUNK>
-__global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
-    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
-    int64_t ntile_i, int64_t njchunk, int64_t nblocks)
+__device__ __forceinline__ void tile_body(
+    T (&tile)[TILE_J][TILE_I + 1], const T *__restrict__ src,
+    T *__restrict__ dst, const DescDev &d, int ta, int64_t ntile_i,
+    int64_t njchunk, int64_t bid)
 {
-    __shared__ T tile[TILE_J][TILE_I + 1];
-
     const int tx = threadIdx.x; /* 0..63  : fast axis */
     const int ty = threadIdx.y; /* 0..NROWS-1 */
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (bid >= nblocks) return;
     const int64_t t_i = bid % ntile_i;
     int64_t rest = bid / ntile_i;
     const int64_t chunk = rest % njchunk;
@@ -242,6 +253,18 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
     }
 }
 
+template <typename T, int TILE_I, int TILE_J, int NROWS, int JCHUNK>
+__global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
+    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
+    int64_t ntile_i, int64_t njchunk, int64_t nblocks)
+{
+    __shared__ T tile[TILE_J][TILE_I + 1];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    tile_body<T, TILE_I, TILE_J, NROWS, JCHUNK>(tile, src, dst, d, ta,
+                                                ntile_i, njchunk, bid);
+}
+
 /* LDS-tiled transpose with VECTOR (16-B) STORES: 64(i) x 128(j) tile, each
  * lane storing a j-pair as one uint4 — 1024-B write bursts per instruction.
  * Interleaved-median probe (profiles/r2_probe_kernels*.txt): +1.5-1.8% over
@@ -250,26 +273,17 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
  * do not).  8-byte elements only; caller guarantees every dst stride
  * (except the unit ta axis) and the dst offset are EVEN and the dst base
  * pointer is 16-B aligned, so every vector store is aligned.  Tail j-tiles
- * (nj < TJ or odd) take a scalar epilogue. */
+ * (nj < TJ or odd) take a scalar epilogue.  Body shared with the grouped
+ * k_group_tile_vs, like tile_body. */
 template <typename T, int TI, int TJ, int NROWS, int JCHUNK>
-__global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs(
-    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
-    int64_t ntile_i, int64_t njchunk, int64_t nblocks)
+__device__ __forceinline__ void tile_vs_body(
+    T (&tile)[TI][TJ + 2], const T *__restrict__ src, T *__restrict__ dst,
+    const DescDev &d, int ta, int64_t ntile_i, int64_t njchunk, int64_t bid)
 {
     static_assert(sizeof(T) == 8, "vector-store tile is 8-byte-elem only");
-    /* TRANSPOSED LDS layout (tile[i][j], +2 pad): the store phase reads
-     * 16 B of consecutive j per lane — one wide conflict-free LDS read.
-     * The original tile[j][i] layout measured 0.6 LDS-conflict cycles per
-     * active cycle (lane-pair row-strided reads); this layout removes them
-     * and wins the interleaved A/B by a small margin (probe vs2 p2,
-     * profiles/r2_probe_vs2*.txt). */
-    __shared__ T tile[TI][TJ + 2];
-
     const int tx = threadIdx.x;
     const int ty = threadIdx.y;
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (bid >= nblocks) return;
     const int64_t t_i = bid % ntile_i;
     int64_t rest = bid / ntile_i;
     const int64_t chunk = rest % njchunk;
@@ -318,6 +332,24 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs(
         }
         __syncthreads();
     }
+}
+
+template <typename T, int TI, int TJ, int NROWS, int JCHUNK>
+__global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs(
+    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
+    int64_t ntile_i, int64_t njchunk, int64_t nblocks)
+{
+    /* TRANSPOSED LDS layout (tile[i][j], +2 pad): the store phase reads
+     * 16 B of consecutive j per lane — one wide conflict-free LDS read.
+     * The original tile[j][i] layout measured 0.6 LDS-conflict cycles per
+     * active cycle (lane-pair row-strided reads); this layout removes them
+     * and wins the interleaved A/B by a small margin (probe vs2 p2,
+     * profiles/r2_probe_vs2*.txt). */
+    __shared__ T tile[TI][TJ + 2];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    tile_vs_body<T, TI, TJ, NROWS, JCHUNK>(tile, src, dst, d, ta, ntile_i,
+                                           njchunk, bid);
 }
 
 /* LDS-tiled transpose for 1- and 2-byte elements with PACKED (8-B) global
@@ -523,6 +555,85 @@ __global__ __launch_bounds__(256) void k_transpose_tile_wide(
             }
         }
     }
+}
+
+/* ---- grouped kernels: one launch over a table of descriptors ----------
+ *
+ * A stage of a multi-field transpose (every pack, or every unpack, of every
+ * field) is a table of entries in device memory; one launch covers all
+ * entries that run the same kernel instance.  The flat block ids of the
+ * launch are split among the entries: entry e owns [first[e], first[e+1]).
+ * A workgroup finds its entry by a binary search over `first` and then runs
+ * the body of the single-descriptor kernel on its entry-local block id.
+ *
+ * The search reads only blockIdx, gridDim and kernel arguments, so the entry
+ * index is the same for every lane; readfirstlane states that to the
+ * compiler, which keeps the index, the entry's address and every descriptor
+ * field it loads on scalar registers. */
+struct GEntry {
+    DescDev d;       /* offsets relative to src/dst, in kernel words */
+    const void *src; /* base pointers baked in: the table is per array set */
+    void *dst;
+    int ta;                   /* tile kernels */
+    int64_t ntile_i, njchunk; /* tile kernels */
+};
+
+__device__ __forceinline__ int group_find(const int64_t *__restrict__ first,
+                                          int nent, int64_t bid)
+{
+    int lo = 0, hi = nent; /* first[lo] <= bid < first[hi] */
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= bid)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+/* COPY_1D and LINEAR entries of one word size (a 1-D copy is a linear copy
+ * with no outer axes) */
+template <typename T>
+__global__ __launch_bounds__(256) void k_group_linear(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    linear_body<T>((const T *)g.src, (T *)g.dst, g.d, bid - first[e]);
+}
+
+template <typename T, int TILE_I, int TILE_J, int NROWS>
+__global__ __launch_bounds__(64 * NROWS) void k_group_tile(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    __shared__ T tile[TILE_J][TILE_I + 1];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    tile_body<T, TILE_I, TILE_J, NROWS, 1>(tile, (const T *)g.src,
+                                           (T *)g.dst, g.d, g.ta, g.ntile_i,
+                                           g.njchunk, bid - first[e]);
+}
+
+template <typename T, int TI, int TJ, int NROWS>
+__global__ __launch_bounds__(64 * NROWS) void k_group_tile_vs(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    __shared__ T tile[TI][TJ + 2];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    tile_vs_body<T, TI, TJ, NROWS, 1>(tile, (const T *)g.src, (T *)g.dst,
+                                      g.d, g.ta, g.ntile_i, g.njchunk,
+                                      bid - first[e]);
 }
 
 /* ================= descriptor normalization & dispatch ============= */
@@ -1266,6 +1377,8 @@ struct PeerBlockC {
     bool has_unpack_raw = false;
 };
 
+struct StageTable; /* multi-field stage: launch list + device tables */
+
 struct pa_plan {
     pa_pencil Pi, Po;
     int rank;
@@ -1310,7 +1423,13 @@ struct pa_plan {
     hipEvent_t tm[7] = {nullptr, nullptr, nullptr, nullptr,
                         nullptr, nullptr, nullptr};
     bool tm_valid[7] = {false, false, false, false, false, false, false};
+    /* multi-field stages (pa_transpose_*_many): LRU of built stage tables,
+     * keyed on (n, stage, every pointer the stage touches) */
+    std::vector<StageTable *> tables;
+    uint64_t table_clock = 0;
 };
+
+static void free_stage_tables(pa_plan *p);
 
 static int64_t prod_extra(const pa_plan &pl)
 {
@@ -1854,6 +1973,7 @@ void pa_plan_destroy(pa_plan *p)
     for (auto e : p->tm)
         if (e) (void)hipEventDestroy(e);
     if (p->comm_stream) (void)hipStreamDestroy(p->comm_stream);
+    free_stage_tables(p);
     delete p;
 }
 
@@ -1880,6 +2000,7 @@ pa_status pa_plan_buffer_sizes(const pa_plan *p, int64_t *send_bytes,
 
 pa_status pa_plan_set_buffers(pa_plan *p, void *send_buf, void *recv_buf)
 {
+    free_stage_tables(p); /* tables bake the staging pointers in */
     if (p->own_bufs) {
         if (p->send_buf) (void)hipFree(p->send_buf);
         if (p->recv_buf) (void)hipFree(p->recv_buf);
@@ -2230,6 +2351,591 @@ pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
     out[2] = k.byteified;
     out[3] = k.sweep;
     out[4] = k.m;
+    return 0;
+}
+
+} /* extern "C" */
+
+/* ================= multi-field transposes ========================== */
+/* n fields of one pencil pair in one call: one grouped launch per stage
+ * and kernel signature, one message per peer carrying all n fields, and
+ * the stages exposed separately so a host can run its own exchange.
+ *
+ * Staging layout: a staging block at element offset o with c elements in
+ * the single-field plan holds field f at n*o + f*c.  Blocks are
+ * consecutive, so this tiles the n-fold buffer exactly and peer k's message
+ * is the contiguous range [n*o_k, n*(o_k + c_k)). */
+
+enum {
+    STAGE_PACK = PA_STAGE_PACK,
+    STAGE_LOCAL = PA_STAGE_LOCAL,
+    STAGE_UNPACK = PA_STAGE_UNPACK
+};
+
+static inline int64_t many_shift(int n, int f, int64_t o, int64_t c)
+{
+    return (int64_t)(n - 1) * o + (int64_t)f * c;
+}
+
+/* the descriptor of field f: the single-field one with its staging-side
+ * offset moved; `which` as in pa_plan_copydesc (0..4) */
+static pa_status many_desc(const pa_plan *p, int n, int f, int which, int k,
+                           CopyDescH *out)
+{
+    if (n < 1) return fail("n must be >= 1");
+    if (f < 0 || f >= n) return fail("field %d out of range", f);
+    if (which == 0) {
+        if (!p->has_local) return fail("no local copy in plan");
+        *out = p->local;
+        return 0;
+    }
+    if (which == 3 || which == 4) {
+        if (!p->has_self) return fail("no staged self block in plan");
+        const int64_t sh =
+            many_shift(n, f, p->self_pack.doff, p->self_pack.total);
+        *out = which == 3 ? p->self_pack : p->self_unpack;
+        if (which == 3)
+            out->doff += sh;
+        else
+            out->soff += sh;
+        return 0;
+    }
+    if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
+        return fail("no peer block %d", k);
+    const PeerBlockC &b = p->peers[k];
+    if (which == 1) {
+        if (!b.has_pack) return fail("no pack for peer %d", k);
+        *out = b.pack;
+        out->doff += many_shift(n, f, b.send_off, b.send_n);
+        return 0;
+    }
+    if (which == 2) {
+        if (!b.has_unpack) return fail("no unpack for peer %d", k);
+        *out = b.unpack;
+        out->soff += many_shift(n, f, b.recv_off, b.recv_n);
+        return 0;
+    }
+    return fail("bad which %d", which);
+}
+
+struct StageItem {
+    KernelSel k;
+    const void *src;
+    void *dst;
+    int64_t nti = 0, njc = 0, nblocks = 0;
+};
+
+struct StageLaunch {
+    int kind = 0, word = 0;
+    bool grouped = false;
+    std::vector<int> items;
+    int64_t nblocks = 0;
+    void *d_mem = nullptr; /* grouped: first[nent] then GEntry[nent] */
+};
+
+struct StageTable {
+    std::vector<uintptr_t> key;
+    std::vector<StageItem> items;
+    std::vector<StageLaunch> launches;
+    uint64_t stamp = 0;
+};
+
+#define PA_STAGE_TABLES_MAX 12
+
+/* workgroups of one selection, and the tile counts the tile kernels take:
+ * the grid launch_sel() launches for it */
+static void sel_grid(const KernelSel &k, StageItem *it)
+{
+    const CopyDescH &w = k.d;
+    it->nti = it->njc = 0;
+    int ti = 0, tj = 0;
+    switch (k.kind) {
+    case PA_KERNEL_NONE:
+        it->nblocks = 0;
+        return;
+    case PA_KERNEL_COPY_1D:
+    case PA_KERNEL_COPY_1D_NT:
+    case PA_KERNEL_LINEAR:
+        it->nblocks = grid_exact(w.total, 256);
+        return;
+    case PA_KERNEL_GENERIC:
+        it->nblocks = grid_for(w.total, 256);
+        return;
+    case PA_KERNEL_TILE:
+        ti = k.word == 16 ? 32 : 128;
+        tj = k.word == 16 ? 32 : 64;
+        break;
+    case PA_KERNEL_TILE_VS:
+        ti = 64;
+        tj = 128;
+        break;
+    case PA_KERNEL_TILE_PK:
+        ti = tj = 128;
+        break;
+    default: /* PA_KERNEL_TILE_WIDE */
+        ti = k.ti;
+        tj = k.tj;
+        break;
+    }
+    int64_t nbatch = 1;
+    for (int a = 1; a < w.nd; a++)
+        if (a != k.ta) nbatch *= w.dims[a];
+    const int64_t ntj = (w.dims[k.ta] + tj - 1) / tj;
+    it->nti = (w.dims[0] + ti - 1) / ti;
+    it->njc = (ntj + k.sweep - 1) / k.sweep;
+    it->nblocks = it->nti * it->njc * nbatch;
+}
+
+/* kinds with a grouped kernel; everything else launches per entry */
+static bool sel_groupable(const KernelSel &k, int *sig_kind)
+{
+    if (k.kind == PA_KERNEL_COPY_1D || k.kind == PA_KERNEL_LINEAR) {
+        *sig_kind = PA_KERNEL_LINEAR;
+        return true;
+    }
+    if ((k.kind == PA_KERNEL_TILE || k.kind == PA_KERNEL_TILE_VS) &&
+        k.sweep == 1) {
+        *sig_kind = k.kind;
+        return true;
+    }
+    return false;
+}
+
+/* The launch list of one stage: select_kernel_comp() per entry, entries of
+ * one signature (kind, word) share a grouped launch.  Host-only; pointers
+ * are used for alignment only. */
+static pa_status build_stage(const pa_plan *p, int n, int stage,
+                             const void *const *srcs, void *const *dsts,
+                             const void *send_buf, void *recv_buf,
+                             StageTable *t)
+{
+    auto add = [&](int f, int which, int k, const void *src,
+                   void *dst) -> pa_status {
+        CopyDescH d;
+        if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
+        StageItem it;
+        if (pa_status st =
+                select_kernel_comp(d, p->ssz, p->ncomp, src, dst, &it.k))
+            return st;
+        it.src = src;
+        it.dst = dst;
+        sel_grid(it.k, &it);
+        if (it.nblocks == 0) return 0; /* empty: contributes no blocks */
+        int sig = 0;
+        const bool grp = sel_groupable(it.k, &sig);
+        const int idx = (int)t->items.size();
+        t->items.push_back(it);
+        if (grp)
+            for (auto &l : t->launches)
+                if (l.grouped && l.kind == sig && l.word == it.k.word) {
+                    l.items.push_back(idx);
+                    l.nblocks += it.nblocks;
+                    return 0;
+                }
+        StageLaunch l;
+        l.kind = grp ? sig : it.k.kind;
+        l.word = it.k.word;
+        l.grouped = grp;
+        l.items.push_back(idx);
+        l.nblocks = it.nblocks;
+        t->launches.push_back(l);
+        return 0;
+    };
+
+    for (int f = 0; f < n; f++) {
+        const void *src = srcs ? srcs[f] : nullptr;
+        void *dst = dsts ? dsts[f] : nullptr;
+        if (stage == STAGE_PACK) {
+            for (auto &b : p->peers)
+                if (b.has_pack)
+                    if (pa_status st = add(f, 1, b.k, src, (void *)send_buf))
+                        return st;
+            if (p->has_self)
+                if (pa_status st = add(f, 3, 0, src, recv_buf)) return st;
+        } else if (stage == STAGE_LOCAL) {
+            if (p->has_local)
+                if (pa_status st = add(f, 0, 0, src, dst)) return st;
+            if (p->has_self)
+                if (pa_status st = add(f, 4, 0, recv_buf, dst)) return st;
+        } else {
+            for (auto &b : p->peers)
+                if (b.has_unpack)
+                    if (pa_status st = add(f, 2, b.k, recv_buf, dst))
+                        return st;
+        }
+    }
+    return 0;
+}
+
+static void free_table(StageTable *t)
+{
+    /* hipFree waits for the device, so no launch still reads the table */
+    for (auto &l : t->launches)
+        if (l.d_mem) (void)hipFree(l.d_mem);
+    delete t;
+}
+
+static void free_stage_tables(pa_plan *p)
+{
+    for (auto *t : p->tables) free_table(t);
+    p->tables.clear();
+}
+
+/* write the device tables of the grouped launches: a fresh allocation and
+ * one blocking copy each, never modified afterwards */
+static pa_status upload_stage(StageTable *t)
+{
+    for (auto &l : t->launches) {
+        if (!l.grouped) continue;
+        const size_t ne = l.items.size();
+        std::vector<char> host(ne * sizeof(int64_t) + ne * sizeof(GEntry));
+        int64_t *first = (int64_t *)host.data();
+        GEntry *ent = (GEntry *)(host.data() + ne * sizeof(int64_t));
+        int64_t acc = 0;
+        for (size_t i = 0; i < ne; i++) {
+            const StageItem &it = t->items[l.items[i]];
+            first[i] = acc;
+            acc += it.nblocks;
+            GEntry g;
+            memset(&g, 0, sizeof g);
+            g.d = to_dev(it.k.d);
+            g.src = it.src;
+            g.dst = it.dst;
+            g.ta = it.k.ta;
+            g.ntile_i = it.nti;
+            g.njchunk = it.njc;
+            memcpy(&ent[i], &g, sizeof g);
+        }
+        HIP_CHECK(hipMalloc(&l.d_mem, host.size()));
+        HIP_CHECK(hipMemcpy(l.d_mem, host.data(), host.size(),
+                            hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+static pa_status launch_group(const StageLaunch &l, hipStream_t stream)
+{
+    const int ne = (int)l.items.size();
+    const int64_t *first = (const int64_t *)l.d_mem;
+    const GEntry *ent =
+        (const GEntry *)((const char *)l.d_mem + ne * sizeof(int64_t));
+    const int W = l.word;
+    dim3 grid;
+#define GROUP_GRID(threads)                                                  \
+    do {                                                                     \
+        if (pa_status gst = grid2d(l.nblocks, threads, &grid)) return gst;   \
+    } while (0)
+#define GROUP_LAUNCH(kern, block)                                            \
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
+                       l.nblocks)
+    if (l.kind == PA_KERNEL_LINEAR) {
+        GROUP_GRID(256);
+        if (W == 16)
+            GROUP_LAUNCH(k_group_linear<uint4>, dim3(256));
+        else if (W == 8)
+            GROUP_LAUNCH(k_group_linear<uint64_t>, dim3(256));
+        else if (W == 4)
+            GROUP_LAUNCH(k_group_linear<uint32_t>, dim3(256));
+        else if (W == 2)
+            GROUP_LAUNCH(k_group_linear<uint16_t>, dim3(256));
+        else
+            GROUP_LAUNCH(k_group_linear<uint8_t>, dim3(256));
+    } else if (l.kind == PA_KERNEL_TILE_VS) {
+        GROUP_GRID(64 * 16);
+        GROUP_LAUNCH((k_group_tile_vs<uint64_t, 64, 128, 16>), dim3(64, 16));
+    } else if (l.kind == PA_KERNEL_TILE) {
+        if (W == 16) {
+            GROUP_GRID(64 * 8);
+            GROUP_LAUNCH((k_group_tile<uint4, 32, 32, 8>), dim3(64, 8));
+        } else {
+            GROUP_GRID(64 * 16);
+            if (W == 8)
+                GROUP_LAUNCH((k_group_tile<uint64_t, 128, 64, 16>),
+                             dim3(64, 16));
+            else if (W == 4)
+                GROUP_LAUNCH((k_group_tile<uint32_t, 128, 64, 16>),
+                             dim3(64, 16));
+            else if (W == 2)
+                GROUP_LAUNCH((k_group_tile<uint16_t, 128, 64, 16>),
+                             dim3(64, 16));
+            else
+                GROUP_LAUNCH((k_group_tile<uint8_t, 128, 64, 16>),
+                             dim3(64, 16));
+        }
+    } else
+        return fail("bad grouped kind %d", l.kind);
+#undef GROUP_GRID
+#undef GROUP_LAUNCH
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static void stage_key(const pa_plan *p, int n, int stage,
+                      const void *const *srcs, void *const *dsts,
+                      std::vector<uintptr_t> *key)
+{
+    key->clear();
+    key->push_back((uintptr_t)n);
+    key->push_back((uintptr_t)stage);
+    key->push_back((uintptr_t)p->send_buf);
+    key->push_back((uintptr_t)p->recv_buf);
+    for (int f = 0; f < n; f++) {
+        key->push_back(stage != STAGE_UNPACK ? (uintptr_t)srcs[f] : 0);
+        key->push_back(stage != STAGE_PACK ? (uintptr_t)dsts[f] : 0);
+    }
+}
+
+static pa_status many_check(const pa_plan *p, int n, int stage,
+                            const void *const *srcs, void *const *dsts)
+{
+    if (!p) return fail("null plan");
+    if (n < 1) return fail("n must be >= 1 (got %d)", n);
+    if (stage != STAGE_UNPACK) {
+        if (!srcs) return fail("null srcs");
+        for (int f = 0; f < n; f++)
+            if (!srcs[f]) return fail("null src pointer for field %d", f);
+    }
+    if (stage != STAGE_PACK) {
+        if (!dsts) return fail("null dsts");
+        for (int f = 0; f < n; f++)
+            if (!dsts[f]) return fail("null dst pointer for field %d", f);
+    }
+    if (p->own_bufs)
+        return fail("multi-field stages need staging buffers of "
+                    "pa_plan_buffer_sizes_many bytes from pa_plan_set_buffers");
+    if ((p->send_total > 0 && !p->send_buf) ||
+        (p->recv_total > 0 && !p->recv_buf))
+        return fail("missing staging buffers: call pa_plan_set_buffers with "
+                    "pa_plan_buffer_sizes_many bytes");
+    return 0;
+}
+
+static pa_status run_stage(pa_plan *p, int n, int stage,
+                           const void *const *srcs, void *const *dsts,
+                           hipStream_t stream)
+{
+    if (pa_status st = many_check(p, n, stage, srcs, dsts)) return st;
+    std::vector<uintptr_t> key;
+    stage_key(p, n, stage, srcs, dsts, &key);
+    StageTable *t = nullptr;
+    for (auto *c : p->tables)
+        if (c->key == key) { t = c; break; }
+    if (!t) {
+        if ((int)p->tables.size() >= PA_STAGE_TABLES_MAX) {
+            size_t old = 0;
+            for (size_t i = 1; i < p->tables.size(); i++)
+                if (p->tables[i]->stamp < p->tables[old]->stamp) old = i;
+            free_table(p->tables[old]);
+            p->tables.erase(p->tables.begin() + old);
+        }
+        t = new StageTable;
+        t->key = key;
+        pa_status st = build_stage(p, n, stage, srcs, dsts, p->send_buf,
+                                   p->recv_buf, t);
+        if (!st) st = upload_stage(t);
+        if (st) { free_table(t); return st; }
+        p->tables.push_back(t);
+    }
+    t->stamp = ++p->table_clock;
+    for (auto &l : t->launches) {
+        pa_status st;
+        if (l.grouped)
+            st = launch_group(l, stream);
+        else {
+            const StageItem &it = t->items[l.items[0]];
+            st = launch_sel(it.k, it.src, it.dst, stream);
+        }
+        if (st) return st;
+    }
+    return 0;
+}
+
+extern "C" {
+
+pa_status pa_plan_buffer_sizes_many(const pa_plan *p, int n,
+                                    int64_t *send_bytes, int64_t *recv_bytes)
+{
+    if (!p || !send_bytes || !recv_bytes) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1 (got %d)", n);
+    *send_bytes = (int64_t)n * p->send_total * p->esz;
+    *recv_bytes = (int64_t)n * p->recv_total * p->esz;
+    return 0;
+}
+
+pa_status pa_plan_peer_message(const pa_plan *p, int n, int k, int64_t out[4])
+{
+    if (!p || !out) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1 (got %d)", n);
+    if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
+        return fail("no peer block %d", k);
+    const PeerBlockC &b = p->peers[k];
+    if (k == p->myk) { /* the self block is never a message */
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return 0;
+    }
+    out[0] = (int64_t)n * b.send_off * p->esz;
+    out[1] = (int64_t)n * b.send_n * p->esz;
+    out[2] = (int64_t)n * b.recv_off * p->esz;
+    out[3] = (int64_t)n * b.recv_n * p->esz;
+    return 0;
+}
+
+pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
+                                int k, int64_t *nd, int64_t *dims,
+                                int64_t *sstr, int64_t *soff, int64_t *dstr,
+                                int64_t *doff)
+{
+    if (!p) return fail("null plan");
+    CopyDescH d;
+    if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
+    *nd = d.nd;
+    for (int i = 0; i < d.nd; i++) {
+        dims[i] = d.dims[i];
+        sstr[i] = d.sstr[i];
+        dstr[i] = d.dstr[i];
+    }
+    *soff = d.soff;
+    *doff = d.doff;
+    return 0;
+}
+
+pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
+                                 const void *const *srcs, void *const *dsts,
+                                 int max_rows, int64_t (*rows)[4], int *nrows)
+{
+    if (!p || !nrows) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1 (got %d)", n);
+    if (stage < STAGE_PACK || stage > STAGE_UNPACK)
+        return fail("bad stage %d", stage);
+    /* staging as set, else assumed 256-byte aligned; never dereferenced */
+    const void *send = p->send_buf ? p->send_buf : (const void *)256;
+    void *recv = p->recv_buf ? p->recv_buf : (void *)256;
+    std::vector<const void *> s(n, (const void *)256);
+    std::vector<void *> d(n, (void *)256);
+    for (int f = 0; f < n; f++) {
+        if (srcs && srcs[f]) s[f] = srcs[f];
+        if (dsts && dsts[f]) d[f] = dsts[f];
+    }
+    StageTable t;
+    if (pa_status st =
+            build_stage(p, n, stage, s.data(), d.data(), send, recv, &t))
+        return st;
+    *nrows = (int)t.launches.size();
+    for (int i = 0; i < *nrows && i < max_rows; i++) {
+        const StageLaunch &l = t.launches[i];
+        rows[i][0] = l.kind;
+        rows[i][1] = l.grouped ? 1 : 0;
+        rows[i][2] = (int64_t)l.items.size();
+        rows[i][3] = l.nblocks;
+    }
+    return 0;
+}
+
+int pa_plan_stage_table_count(const pa_plan *p)
+{
+    return p ? (int)p->tables.size() : 0;
+}
+
+pa_status pa_transpose_pack_many(pa_plan *p, int n, const void *const *srcs,
+                                 void *stream)
+{
+    return run_stage(p, n, STAGE_PACK, srcs, nullptr, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_local_many(pa_plan *p, int n, const void *const *srcs,
+                                  void *const *dsts, void *stream)
+{
+    return run_stage(p, n, STAGE_LOCAL, srcs, dsts, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_unpack_many(pa_plan *p, int n, void *const *dsts,
+                                   void *stream)
+{
+    return run_stage(p, n, STAGE_UNPACK, nullptr, dsts, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_execute_many(pa_plan *p, int n,
+                                    const void *const *srcs,
+                                    void *const *dsts, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (pa_status st = many_check(p, n, STAGE_LOCAL, srcs, dsts)) return st;
+
+    bool exchanging = false;
+    if (p->R >= 0 && p->P > 1)
+        for (auto &blk : p->peers)
+            if (blk.k != p->myk && (blk.send_n || blk.recv_n))
+                exchanging = true;
+    if (exchanging && !p->comm)
+        return fail("subgroup exchange requires pa_plan_set_comm");
+
+    if (p->timing) {
+        for (auto &e : p->tm)
+            if (!e) HIP_CHECK(hipEventCreate(&e));
+        for (auto &v : p->tm_valid) v = false;
+    }
+#define TM_REC(i, strm)                                                      \
+    do {                                                                     \
+        if (p->timing) {                                                     \
+            HIP_CHECK(hipEventRecord(p->tm[i], strm));                       \
+            p->tm_valid[i] = true;                                           \
+        }                                                                    \
+    } while (0)
+
+    /* 1. every pack and staged self pack of every field, before any write
+     * of a destination */
+    TM_REC(0, stream);
+    if (pa_status st = run_stage(p, n, STAGE_PACK, srcs, nullptr, stream))
+        return st;
+    TM_REC(1, stream);
+
+    /* 2. one grouped exchange, one message per peer carrying all n fields,
+     * on the comm stream, event-ordered like pa_transpose_execute */
+    if (exchanging) {
+        if (!p->comm_stream) {
+            HIP_CHECK(hipStreamCreateWithFlags(&p->comm_stream,
+                                               hipStreamNonBlocking));
+            HIP_CHECK(hipEventCreateWithFlags(&p->ev_pack,
+                                              hipEventDisableTiming));
+            HIP_CHECK(hipEventCreateWithFlags(&p->ev_comm,
+                                              hipEventDisableTiming));
+        }
+        HIP_CHECK(hipEventRecord(p->ev_pack, stream));
+        HIP_CHECK(hipStreamWaitEvent(p->comm_stream, p->ev_pack, 0));
+        TM_REC(3, p->comm_stream);
+        NCCL_CHECK(ncclGroupStart());
+        for (auto &blk : p->peers) {
+            if (blk.k == p->myk) continue;
+            int64_t m[4];
+            if (pa_status st = pa_plan_peer_message(p, n, blk.k, m))
+                return st;
+            if (m[3])
+                NCCL_CHECK(ncclRecv((char *)p->recv_buf + m[2], (size_t)m[3],
+                                    ncclUint8, blk.k, p->comm->comm,
+                                    p->comm_stream));
+            if (m[1])
+                NCCL_CHECK(ncclSend((const char *)p->send_buf + m[0],
+                                    (size_t)m[1], ncclUint8, blk.k,
+                                    p->comm->comm, p->comm_stream));
+        }
+        NCCL_CHECK(ncclGroupEnd());
+        TM_REC(4, p->comm_stream);
+        HIP_CHECK(hipEventRecord(p->ev_comm, p->comm_stream));
+    }
+
+    /* 3. fused local copies (aliased: staged self unpacks), overlapping the
+     * exchange on the caller's stream */
+    if (pa_status st = run_stage(p, n, STAGE_LOCAL, srcs, dsts, stream))
+        return st;
+    TM_REC(2, stream);
+
+    /* 4. unpack every received block of every field */
+    if (exchanging) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
+    TM_REC(5, stream);
+    if (pa_status st = run_stage(p, n, STAGE_UNPACK, nullptr, dsts, stream))
+        return st;
+    TM_REC(6, stream);
+#undef TM_REC
     return 0;
 }
 

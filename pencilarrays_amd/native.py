@@ -80,6 +80,17 @@ class KernelKind(NamedTuple):
     words_per_element: int = 1
 
 
+STAGE_PACK, STAGE_LOCAL, STAGE_UNPACK = 0, 1, 2
+
+
+class StageLaunch(NamedTuple):
+    """One launch of a multi-field stage (pa_plan_stage_launches)."""
+    kind: int
+    grouped: bool
+    entries: int
+    workgroups: int
+
+
 def _desc_fields(desc):
     if hasattr(desc, "sstrides"):
         return (desc.dims, desc.sstrides, desc.soffset, desc.dstrides,
@@ -247,6 +258,95 @@ class NativePlan:
         n = nd.value
         return (tuple(dims[:n]), tuple(sstr[:n]), soff.value,
                 tuple(dstr[:n]), doff.value)
+
+    # ---- multi-field transposes (pa_*_many) ----------------------------
+
+    @staticmethod
+    def _ptrs(ptrs, n):
+        if ptrs is None:
+            return None
+        if len(ptrs) != n:
+            raise ValueError(f"expected {n} pointers, got {len(ptrs)}")
+        return (VP * n)(*[VP(int(q)) for q in ptrs])
+
+    def buffer_sizes_many(self, n: int) -> Tuple[int, int]:
+        s, r = I64(), I64()
+        _check(self.lib, self.lib.pa_plan_buffer_sizes_many(
+            self._plan, n, ctypes.byref(s), ctypes.byref(r)),
+            "pa_plan_buffer_sizes_many")
+        return s.value, r.value
+
+    def peer_message(self, n: int, k: int) -> Tuple[int, int, int, int]:
+        """(send_off, send_bytes, recv_off, recv_bytes) of the one message
+        exchanged with peer ``k`` for ``n`` fields."""
+        out = (I64 * 4)()
+        _check(self.lib, self.lib.pa_plan_peer_message(self._plan, n, k, out),
+               "pa_plan_peer_message")
+        return tuple(int(v) for v in out)
+
+    def pack_many(self, src_ptrs, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_pack_many(
+            self._plan, n, self._ptrs(src_ptrs, n), VP(stream)),
+            "pa_transpose_pack_many")
+
+    def local_many(self, src_ptrs, dst_ptrs, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_local_many(
+            self._plan, n, self._ptrs(src_ptrs, n), self._ptrs(dst_ptrs, n),
+            VP(stream)), "pa_transpose_local_many")
+
+    def unpack_many(self, dst_ptrs, stream: int = 0):
+        n = len(dst_ptrs)
+        _check(self.lib, self.lib.pa_transpose_unpack_many(
+            self._plan, n, self._ptrs(dst_ptrs, n), VP(stream)),
+            "pa_transpose_unpack_many")
+
+    def execute_many(self, src_ptrs, dst_ptrs, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_execute_many(
+            self._plan, n, self._ptrs(src_ptrs, n), self._ptrs(dst_ptrs, n),
+            VP(stream)), "pa_transpose_execute_many")
+
+    def stage_table_count(self) -> int:
+        """Stage tables in the plan's cache (pa_plan_stage_table_count)."""
+        return int(self.lib.pa_plan_stage_table_count(self._plan))
+
+    def copydesc_many(self, n: int, f: int, which: int, k: int = 0):
+        nd = I64()
+        dims = (I64 * 8)()
+        sstr = (I64 * 8)()
+        dstr = (I64 * 8)()
+        soff = I64()
+        doff = I64()
+        st = self.lib.pa_plan_copydesc_many(
+            self._plan, n, f, which, k, ctypes.byref(nd), dims, sstr,
+            ctypes.byref(soff), dstr, ctypes.byref(doff))
+        if st != 0:
+            return None
+        m = nd.value
+        return (tuple(dims[:m]), tuple(sstr[:m]), soff.value,
+                tuple(dstr[:m]), doff.value)
+
+    def stage_launches(self, n: int, stage: int, src_ptrs=None,
+                       dst_ptrs=None):
+        """The launches stage ``stage`` (STAGE_PACK / STAGE_LOCAL /
+        STAGE_UNPACK) makes for ``n`` fields: a list of
+        :class:`StageLaunch`.  Host-only; pointers (optional) are used for
+        alignment only."""
+        cap = 64
+        while True:
+            rows = ((I64 * 4) * cap)()
+            nrows = ctypes.c_int()
+            _check(self.lib, self.lib.pa_plan_stage_launches(
+                self._plan, n, stage, self._ptrs(src_ptrs, n),
+                self._ptrs(dst_ptrs, n), cap, rows, ctypes.byref(nrows)),
+                "pa_plan_stage_launches")
+            if nrows.value <= cap:
+                break
+            cap = nrows.value
+        return [StageLaunch(int(r[0]), bool(r[1]), int(r[2]), int(r[3]))
+                for r in rows[:nrows.value]]
 
     def __del__(self):
         lib = getattr(self, "lib", None)
@@ -483,5 +583,64 @@ class NativeTransposition:
         stream = torch.cuda.current_stream().cuda_stream
         self.native.execute(src_tensor.data_ptr(), dst_tensor.data_ptr(),
                             stream)
+        if sync:
+            self.native.wait(stream)
+
+
+class NativeMultiTransposition:
+    """GPU execution of one MultiTransposition: ``n`` fields of one pencil
+    pair through ONE native plan (pa_transpose_execute_many).  Staging is
+    ``n`` times the plan's sizes, reserved from the shared StagingPool and
+    re-pointed when the pool grows, like NativeTransposition."""
+
+    def __init__(self, mt):
+        import torch
+        self.torch = torch
+        plan = mt.plan
+        src = mt.srcs[0]
+        self.n = len(mt.srcs)
+        self.native = NativePlan(plan.Pi, plan.Po, plan.rank,
+                                 src.data.element_size(), plan.extra_dims,
+                                 aliased=plan.aliased, ncomp=src.ncomp)
+        sb, rb = self.native.buffer_sizes_many(self.n)
+        dev = src.data.device
+        self._need = (max(sb, 1), max(rb, 1))
+        if os.environ.get("PENCILHIP_PRIVATE_STAGING") == "1":
+            self._pool = None
+            self._send = torch.empty(self._need[0], dtype=torch.uint8,
+                                     device=dev)
+            self._recv = torch.empty(self._need[1], dtype=torch.uint8,
+                                     device=dev)
+            self.native.set_buffers(self._send.data_ptr(),
+                                    self._recv.data_ptr())
+        else:
+            self._pool = staging_pool(dev)
+            self._bind_pool()
+        if self.native.nproc_sub > 1:
+            comm = subgroup_comm(plan.Pi.topology, self.native.r_dim,
+                                 plan.rank)
+            if comm is not None:
+                self.native.set_comm(comm)
+
+    def _bind_pool(self):
+        send, recv = self._pool.reserve(*self._need)
+        if (getattr(self, "_send", None) is not send
+                or getattr(self, "_recv", None) is not recv):
+            # set_buffers drops the engine's stage tables, so only re-point
+            # when the pool really handed out other tensors
+            self._send, self._recv = send, recv
+            self.native.set_buffers(send.data_ptr(), recv.data_ptr())
+        self._pool_version = self._pool.version
+
+    def execute(self, src_tensors, dst_tensors, sync: bool = True):
+        torch = self.torch
+        for t in list(src_tensors) + list(dst_tensors):
+            assert t.is_cuda and t.is_contiguous()
+        if self._pool is not None and \
+                self._pool.version != self._pool_version:
+            self._bind_pool()  # another plan grew the pool: re-point
+        stream = torch.cuda.current_stream().cuda_stream
+        self.native.execute_many([t.data_ptr() for t in src_tensors],
+                                 [t.data_ptr() for t in dst_tensors], stream)
         if sync:
             self.native.wait(stream)

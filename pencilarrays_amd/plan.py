@@ -301,3 +301,89 @@ def build_plan(Pi: Pencil, Po: Pencil, rank: int,
     assert irecv == length_recv_remote
     plan.recv_nelem_total = irecv + (length_self if aliased else 0)
     return plan
+
+
+# --------------------------------------------------------------------------
+# Multi-field staging layout (n fields of one pencil pair, one plan).
+#
+# The plan stays per field in element units; the staging buffers are n times
+# its sizes.  A staging block that starts at element offset ``o`` with ``c``
+# elements in the single-field plan (a peer's send block, a peer's recv
+# block, the aliased self block in the recv tail) holds field ``f`` at
+# ``n*o + f*c``.  Blocks are consecutive, so this tiles the n-fold buffer
+# exactly, and peer k's message is the contiguous range
+# ``[n*o_k, n*(o_k + c_k))``: one send and one recv per peer whatever n is.
+# ``n = 1`` is the single-field layout.
+# --------------------------------------------------------------------------
+
+def many_shift(n: int, f: int, o: int, c: int) -> int:
+    """How far field ``f`` of ``n`` moves the staging-side offset of a block
+    at offset ``o`` with ``c`` elements: ``n*o + f*c - o``."""
+    return (n - 1) * o + f * c
+
+
+def _check_many(n: int, f: int = 0):
+    if n < 1:
+        raise ValueError(f"n must be >= 1 (got {n})")
+    if not 0 <= f < n:
+        raise ValueError(f"field {f} out of range for n = {n}")
+
+
+def copydesc_many(plan: TransposePlan, n: int, f: int, which: int,
+                  k: int = 0) -> Optional[CopyDesc]:
+    """The descriptor of field ``f`` of ``n``; ``which`` as in
+    ``pa_plan_copydesc``: 0 local, 1 pack of peer k, 2 unpack of peer k,
+    3 staged self pack, 4 staged self unpack.  None where the plan has no
+    such descriptor."""
+    _check_many(n, f)
+    if which == 0:
+        return plan.local
+    if which in (3, 4):
+        if plan.self_pack is None:
+            return None
+        sh = many_shift(n, f, plan.self_pack.doffset, plan.self_pack.nelem)
+        d = plan.self_pack if which == 3 else plan.self_unpack
+        if which == 3:
+            return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
+                            d.doffset + sh)
+        return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides,
+                        d.doffset)
+    if plan.r_dim is None or not 0 <= k < len(plan.peers):
+        return None
+    blk = plan.peers[k]
+    if which == 1:
+        d = blk.pack
+        if d is None:
+            return None
+        sh = many_shift(n, f, blk.send_offset, blk.send_nelem)
+        return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
+                        d.doffset + sh)
+    if which == 2:
+        d = blk.unpack
+        if d is None:
+            return None
+        sh = many_shift(n, f, blk.recv_offset, blk.recv_nelem)
+        return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides,
+                        d.doffset)
+    raise ValueError(f"bad which {which}")
+
+
+def buffer_nelem_many(plan: TransposePlan, n: int) -> Tuple[int, int]:
+    """(send, recv) staging sizes in elements for ``n`` fields."""
+    _check_many(n)
+    return n * plan.send_nelem_total, n * plan.recv_nelem_total
+
+
+def peer_message(plan: TransposePlan, n: int,
+                 k: int) -> Tuple[int, int, int, int]:
+    """``(send_off, send_n, recv_off, recv_n)`` in elements of the one message
+    exchanged with subgroup peer ``k`` for ``n`` fields; all zero for the
+    self block, which is never a message."""
+    _check_many(n)
+    if plan.r_dim is None or not 0 <= k < len(plan.peers):
+        raise ValueError(f"no peer block {k}")
+    if k == plan.my_k:
+        return (0, 0, 0, 0)
+    blk = plan.peers[k]
+    return (n * blk.send_offset, n * blk.send_nelem,
+            n * blk.recv_offset, n * blk.recv_nelem)

@@ -27,7 +27,8 @@ import numpy as np
 from .array import PencilArray
 from .copyexec import apply_copy
 from .pencil import Pencil
-from .plan import TransposePlan, build_plan
+from .plan import (TransposePlan, build_plan, buffer_nelem_many,
+                   copydesc_many, peer_message)
 
 MPI_TAG = 42  # Transpositions.jl:469
 
@@ -220,6 +221,123 @@ def transpose_into(dest: PencilArray, src: PencilArray,
     return Transposition(dest, src, method=method).execute()
 
 
+class MultiTransposition:
+    """``n`` separately allocated fields of ONE pencil pair transposed in one
+    call: ``MultiTransposition(dests, srcs)``, pair ``i`` being
+    ``dests[i] <- srcs[i]``.  What a host does with ``n`` ``transpose!``
+    calls (Transpositions.jl:161-180), as one plan: on the GPU one grouped
+    kernel launch per stage and one message per peer carrying all fields
+    (pa_transpose_execute_many).
+
+    Every pair must have the same input pencil, output pencil, rank, element
+    size, ``extra_dims``, ``elem_dims`` and device.  If any source aliases
+    any destination (in-place pairs, or one pair's destination over another
+    pair's source) the plan is aliased: every read of a source is enqueued
+    before any write of a destination.
+
+    numpy arrays run the host mirror — one single-field Transposition per
+    field, which pins the semantics, not the performance."""
+
+    def __init__(self, dests: Sequence[PencilArray],
+                 srcs: Sequence[PencilArray]):
+        dests, srcs = list(dests), list(srcs)
+        if len(dests) != len(srcs):
+            raise ValueError(
+                f"dests and srcs must have the same length: "
+                f"{len(dests)} != {len(srcs)}")
+        if not srcs:
+            raise ValueError("MultiTransposition needs at least one field")
+        s0, d0 = srcs[0], dests[0]
+
+        def same_pencil(a, b):
+            return (tuple(a.topology.dims) == tuple(b.topology.dims)
+                    and tuple(a.size_global) == tuple(b.size_global)
+                    and tuple(a.decomp_dims) == tuple(b.decomp_dims)
+                    and tuple(a.perm) == tuple(b.perm))
+
+        def storage(a):
+            if a.is_torch:
+                return ("torch", a.data.dtype, str(a.data.device))
+            return ("numpy", a.data.dtype, "cpu")
+
+        for i, (d, s) in enumerate(zip(dests, srcs)):
+            if d.extra_dims != s.extra_dims or s.extra_dims != s0.extra_dims:
+                raise ValueError(
+                    f"field {i}: incompatible extra dimensions of "
+                    f"PencilArrays: {s.extra_dims}, {d.extra_dims} != "
+                    f"{s0.extra_dims}")
+            if d.elem_dims != s.elem_dims or s.elem_dims != s0.elem_dims:
+                raise ValueError(
+                    f"field {i}: incompatible element dimensions of "
+                    f"PencilArrays: {s.elem_dims}, {d.elem_dims} != "
+                    f"{s0.elem_dims}")
+            if d.rank != s.rank or s.rank != s0.rank:
+                raise ValueError(
+                    f"field {i}: every array must live on the same rank")
+            if not same_pencil(s.pencil, s0.pencil):
+                raise ValueError(
+                    f"field {i}: source pencil differs from field 0's")
+            if not same_pencil(d.pencil, d0.pencil):
+                raise ValueError(
+                    f"field {i}: destination pencil differs from field 0's")
+            if storage(s) != storage(s0) or storage(d) != storage(s0):
+                raise ValueError(
+                    f"field {i}: every array must have the same backend, "
+                    f"dtype and device: {storage(s)}, {storage(d)} != "
+                    f"{storage(s0)}")
+        self.srcs = srcs
+        self.dests = dests
+        self.aliased = any(_arrays_alias(s.data, d.data)
+                           for s in srcs for d in dests)
+        self.plan: TransposePlan = build_plan(
+            s0.pencil, d0.pencil, s0.rank, s0.extra_dims,
+            aliased=self.aliased)
+        self._native = None
+
+    def _execute_numpy(self):
+        if self.aliased and len(self.srcs) > 1:
+            # a destination may overlap ANOTHER pair's source: read every
+            # source before any destination is written
+            srcs = [PencilArray(s.pencil, s.rank, s.data.copy(),
+                                s.extra_dims, s.elem_dims)
+                    for s in self.srcs]
+        else:
+            srcs = self.srcs
+        for d, s in zip(self.dests, srcs):
+            Transposition(d, s).execute()
+
+    def execute(self, sync: bool = True):
+        """Run the transposes; ``sync=False`` returns with the work enqueued
+        (see :meth:`Transposition.execute`)."""
+        if self.srcs[0].is_torch:
+            if not self.srcs[0].data.is_cuda:
+                raise RuntimeError(
+                    "torch CPU tensors are not a supported backend: use "
+                    "numpy arrays for the CPU host mirror, or cuda tensors "
+                    "for the native engine")
+            from . import native
+            if self._native is None:
+                self._native = native.NativeMultiTransposition(self)
+            self._native.execute([s.data for s in self.srcs],
+                                 [d.data for d in self.dests], sync=sync)
+        else:
+            self._execute_numpy()
+        return self.dests
+
+    def wait(self):
+        """MPI.Waitall(t) (Transpositions.jl:128-131)."""
+        if self._native is not None:
+            import torch
+            self._native.native.wait(torch.cuda.current_stream().cuda_stream)
+        return self
+
+
+def transpose_many_into(dests: Sequence[PencilArray],
+                        srcs: Sequence[PencilArray]):
+    """``transpose!`` of every pair ``dests[i] <- srcs[i]`` in one call."""
+    return MultiTransposition(dests, srcs).execute()
+
+
 # ----------------------------------------------------------------------
 # In-process multi-rank simulation (test harness only): runs every rank's
 # pack/exchange/unpack inside one process, memcpy standing in for the
@@ -227,7 +345,10 @@ def transpose_into(dest: PencilArray, src: PencilArray,
 # ----------------------------------------------------------------------
 
 def run_transpose_sim(dests: Sequence[PencilArray],
-                      srcs: Sequence[PencilArray]) -> None:
+                      srcs: Sequence[PencilArray],
+                      staging_out=None) -> None:
+    """``staging_out``, if a dict, receives the final ``send``/``recv``
+    staging buffers per rank."""
     nranks = len(srcs)
     plans = [build_plan(s.pencil, d.pencil, r, s.extra_dims,
                         aliased=_arrays_alias(s.data, d.data))
@@ -278,3 +399,81 @@ def run_transpose_sim(dests: Sequence[PencilArray],
         for blk in p.peers:
             if blk.unpack is not None:
                 apply_copy(blk.unpack, recv_bufs[r], dflat[r])
+    if staging_out is not None:
+        staging_out["send"] = send_bufs
+        staging_out["recv"] = recv_bufs
+
+
+def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
+                           srcs_per_rank: Sequence[Sequence[PencilArray]],
+                           staging_out=None) -> None:
+    """:func:`run_transpose_sim` for ``n`` fields per rank with the
+    multi-field staging layout (plan.py): every field of a rank is packed
+    into ONE n-fold send buffer, and the exchange is ONE slice copy per peer
+    pair of ``n * c`` elements — the "one message per peer" contract.
+    ``dests_per_rank[r][f]`` / ``srcs_per_rank[r][f]`` is field ``f`` on
+    rank ``r``.  ``staging_out``, if a dict, receives the final
+    ``send``/``recv`` buffers per rank (tests compare them)."""
+    nranks = len(srcs_per_rank)
+    n = len(srcs_per_rank[0])
+    if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
+            any(len(x) != n for x in dests_per_rank):
+        raise ValueError("every rank needs the same number (>= 1) of fields")
+    plans = []
+    for r in range(nranks):
+        s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
+        aliased = any(_arrays_alias(s.data, d.data)
+                      for s in srcs_per_rank[r] for d in dests_per_rank[r])
+        plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
+                                aliased=aliased))
+    sflat = [[s.element_view() for s in row] for row in srcs_per_rank]
+    dflat = [[d.element_view() for d in row] for row in dests_per_rank]
+    dt = sflat[0][0].dtype
+    send_bufs, recv_bufs = [], []
+    for p in plans:
+        ns, nr = buffer_nelem_many(p, n)
+        send_bufs.append(np.empty(ns, dtype=dt))
+        recv_bufs.append(np.empty(nr, dtype=dt))
+
+    # pack every field on every rank (incl. staged self blocks) before any
+    # destination is written
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for blk in p.peers:
+                if blk.pack is not None:
+                    apply_copy(copydesc_many(p, n, f, 1, blk.peer_k),
+                               sflat[r][f], send_bufs[r])
+            if p.self_pack is not None:
+                apply_copy(copydesc_many(p, n, f, 3), sflat[r][f],
+                           recv_bufs[r])
+    for r, p in enumerate(plans):
+        for f in range(n):
+            if p.local is not None:
+                apply_copy(p.local, sflat[r][f], dflat[r][f])
+            elif p.self_unpack is not None:
+                apply_copy(copydesc_many(p, n, f, 4), recv_bufs[r],
+                           dflat[r][f])
+
+    # exchange: ONE slice copy per peer pair, all n fields in it
+    for r, p in enumerate(plans):
+        if p.r_dim is None:
+            continue
+        for blk in p.peers:
+            if blk.peer_k == p.my_k or blk.send_nelem == 0:
+                continue
+            so, sn, _, _ = peer_message(p, n, blk.peer_k)
+            q = plans[blk.global_rank]
+            _, _, ro, rn = peer_message(q, n, p.my_k)
+            assert rn == sn, (r, blk.peer_k, sn, rn)
+            recv_bufs[blk.global_rank][ro:ro + rn] = send_bufs[r][so:so + sn]
+
+    # unpack every field on every rank
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for blk in p.peers:
+                if blk.unpack is not None:
+                    apply_copy(copydesc_many(p, n, f, 2, blk.peer_k),
+                               recv_bufs[r], dflat[r][f])
+    if staging_out is not None:
+        staging_out["send"] = send_bufs
+        staging_out["recv"] = recv_bufs
