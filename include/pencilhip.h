@@ -261,7 +261,17 @@ pa_status pa_allreduce(pa_comm *c, const void *sendbuf, void *recvbuf,
 
 /* ---- standalone device copy (used by tests/benchmarks) --------------- */
 /* Execute one strided-copy descriptor on device (same kernels the plan
- * uses).  All strides/offsets/dims in elements of elem_size bytes. */
+ * uses).  All strides/offsets/dims in elements of elem_size bytes.
+ *
+ * Alignment: src and dst must be aligned to min(elem_size, 16) rounded down
+ * to a power of two (an f64 buffer to 8 bytes, a 12-byte element to 4).
+ * Wider words (16-byte linear copies, the 16-byte vector stores of the
+ * 8-byte tile, the 8-byte accesses of the 1-/2-byte packed tile) are used
+ * only where both base pointers, the offsets and the strides allow them, so
+ * a buffer that starts one element into an allocation is fine.
+ * Precondition, not checked: a 16-byte element needs 16-byte-aligned
+ * pointers; its transpose tile moves 16-byte words and has no narrower
+ * fallback. */
 pa_status pa_device_copy(int nd, const int64_t *dims, const int64_t *sstr,
                          int64_t soff, const int64_t *dstr, int64_t doff,
                          int64_t elem_size, const void *src, void *dst,

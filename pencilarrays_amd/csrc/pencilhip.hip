@@ -780,11 +780,16 @@ static pa_status select_kernel(const CopyDescH &dn, int64_t esz,
 
     const bool lin = (dn.sstr[0] == 1 && dn.dstr[0] == 1);
     if (lin) {
+        /* widest word dividing the run, every stride/offset in bytes, and
+         * both base addresses (a sliced tensor moves the base by one
+         * element) */
+        const uintptr_t ptrs = (uintptr_t)src | (uintptr_t)dst;
         CopyDescH w;
         int64_t W = 0;
         for (int64_t cand : {16, 8, 4})
             if (cand >= esz || (esz % cand) == 0)
-                if (word_scale(dn, esz, cand, &w)) { W = cand; break; }
+                if ((ptrs & (uintptr_t)(cand - 1)) == 0 &&
+                    word_scale(dn, esz, cand, &w)) { W = cand; break; }
         if (!W) { /* odd element size: fall back to bytes */
             if (!word_scale(dn, esz, 1, &w)) return fail("word_scale(1)");
             W = 1;

@@ -214,3 +214,71 @@ def test_accepts_copydesc_objects():
         native.KERNEL_TILE_PK
     # default pointers (0) count as aligned
     assert native.copy_kernel_kind(d, 2).kind == native.KERNEL_TILE_PK
+
+
+# ---- 5. the linear path honours base-pointer alignment ---------------------
+
+def _widest_word(run_bytes, *addrs):
+    """The rule, restated: the widest of {16, 8, 4, 1} bytes that divides
+    the run and every address."""
+    for w in (16, 8, 4, 1):
+        if run_bytes % w == 0 and all(a % w == 0 for a in addrs):
+            return w
+
+
+SHIFTS = {"src": (1, 0), "dst": (0, 1), "both": (1, 1)}
+
+
+@pytest.mark.parametrize("esz", [1, 2, 4, 8])
+@pytest.mark.parametrize("which", sorted(SHIFTS))
+def test_contiguous_copy_word_divides_shifted_pointers(esz, which):
+    """A contiguous run whose base pointer is moved by one element (a sliced
+    tensor) on the src side, the dst side, and both."""
+    ss, ds = SHIFTS[which]
+    sp, dp = PTR + ss * esz, QPTR + ds * esz
+    n = 4096
+    k = kind((n,), (1,), 0, (1,), 0, esz, sp, dp)
+    assert (k.kind, k.byteified) == (native.KERNEL_COPY_1D, 0)
+    assert sp % k.word_bytes == 0 and dp % k.word_bytes == 0, k
+    assert k.word_bytes == _widest_word(n * esz, sp, dp), k
+    # the unshifted copy keeps 16-byte words
+    k = kind((n,), (1,), 0, (1,), 0, esz)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_COPY_1D, 16)
+
+
+@pytest.mark.parametrize("esz", [1, 2, 4, 8])
+@pytest.mark.parametrize("which", sorted(SHIFTS))
+def test_linear_window_word_divides_shifted_pointers(esz, which):
+    """A two-axis linear window (runs of 64 elements, 16-byte-multiple
+    pitches and offsets) from pointers moved by one element."""
+    ss, ds = SHIFTS[which]
+    sp, dp = PTR + ss * esz, QPTR + ds * esz
+    desc = ((64, 16), (1, 96), 32, (1, 80), 16)
+    k = kind(*desc, esz, sp, dp)
+    assert (k.kind, k.byteified) == (native.KERNEL_LINEAR, 0)
+    assert sp % k.word_bytes == 0 and dp % k.word_bytes == 0, k
+    assert k.word_bytes == _widest_word(64 * esz, sp, dp), k
+    k = kind(*desc, esz)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_LINEAR, 16)
+
+
+def test_shifted_pointer_words_issue_examples():
+    k = kind((4096,), (1,), 0, (1,), 0, 1, PTR + 1, QPTR + 3)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_COPY_1D, 1)
+    k = kind((4096,), (1,), 0, (1,), 0, 2, PTR + 2, QPTR)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_COPY_1D, 1)
+    k = kind((32, 16), (1, 40), 0, (1, 32), 0, 8, PTR + 8, QPTR)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_LINEAR, 8)
+    # a pointer that is a multiple of 16 but not of 256 changes nothing
+    k = kind((32, 16), (1, 40), 0, (1, 32), 0, 8, PTR + 16, QPTR + 48)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_LINEAR, 16)
+
+
+@pytest.mark.parametrize("which", sorted(SHIFTS))
+def test_large_copy_from_8mod16_pointer_is_not_nontemporal(which):
+    """The nontemporal copy moves 16-byte words: >= 512 MiB from or to a
+    pointer that is 8 mod 16 takes the plain copy in 8-byte words."""
+    ss, ds = SHIFTS[which]
+    n = (512 << 20) // 8
+    k = kind((n,), (1,), 0, (1,), 0, 8, PTR + 8 * ss, QPTR + 8 * ds)
+    assert (k.kind, k.word_bytes) == (native.KERNEL_COPY_1D, 8)
