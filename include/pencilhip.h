@@ -109,6 +109,45 @@ pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
                               int64_t scalar_size, int64_t ncomp, int e,
                               const int64_t *extra_dims, int rank, int flags,
                               pa_plan **out);
+
+/* Reduced-precision wire: the plan of ncomp scalars of a STORED type per
+ * element whose staging buffers and messages carry a narrower WIRE type — a
+ * field kept in float64 exchanged as float32 halves every message, the
+ * standard lever of pseudo-spectral codes (the reference has no such option;
+ * its transpose! moves eltype(src) as is).  Wire pairs (stored -> wire): */
+#define PA_WIRE_F64_F32  1 /* float64 -> float32  */
+#define PA_WIRE_F32_F16  2 /* float32 -> float16  */
+#define PA_WIRE_F32_BF16 3 /* float32 -> bfloat16 */
+/* What one converting copy does (pa_device_copy_wire): */
+#define PA_WIRE_NARROW 0 /* stored -> wire: every pack, the aliased self pack */
+#define PA_WIRE_WIDEN  1 /* wire -> stored: every unpack, aliased self unpack */
+#define PA_WIRE_ROUND  2 /* stored -> stored through the wire type: the fused
+                          * local copy and same-decomposition plans */
+/* pa_plan_create_wire builds the tables of pa_plan_create_comp(.., stored
+ * scalar size, ncomp, ..): pa_plan_copydesc[_many] return the same
+ * descriptors (element units).  Only byte sizes differ: pa_plan_buffer_sizes,
+ * pa_plan_buffer_sizes_many and pa_plan_peer_message report WIRE bytes, and
+ * the hipMalloc fallback of pa_transpose_execute and the ncclSend/ncclRecv
+ * counts use the wire element size.  ncomp = 1 is a real field, 2 a complex
+ * one (complex128 with PA_WIRE_F64_F32 is complex64 on the wire), and
+ * elem_dims multiply in.
+ * Contract: with round_w(x) = x converted to the wire type (round to nearest
+ * even, subnormals of the wire type kept, beyond its range +-inf, +-0 and
+ * +-inf preserved, NaN stays NaN with sign and payload unspecified) and back,
+ *     dest == T(round_w(src))   bit for bit on every non-NaN element,
+ * T being the transposition of the same plan without a wire pair.  EVERY
+ * element is rounded — the fused local copy, the staged self block of an
+ * aliased plan, a same-decomposition plan — so the result does not depend on
+ * the process grid, and since round_w is idempotent a chain x->y->z rounds
+ * once.  pa_transpose_execute[_many], the three stage calls,
+ * pa_transpose_wait, timing and PA_PLAN_ALIASED work on a wire plan.
+ * PENCILHIP_EXCHANGE_CHUNKS does NOT apply: the exchange is a single group. */
+pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
+                              int wire, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              pa_plan **out);
+/* The wire pair of a plan, or 0 for an ordinary plan. */
+int pa_plan_wire(const pa_plan *p);
 void pa_plan_destroy(pa_plan *p);
 
 /* Subgroup communicator for the exchange (required when the subgroup size
@@ -238,7 +277,8 @@ pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
  * srcs, dsts or single pointers may be NULL (taken as 256-byte aligned).
  * Staging is taken from pa_plan_set_buffers, else assumed 256-byte aligned.
  * At most max_rows rows are written; *nrows is the full count.  The stage
- * calls execute exactly this list. */
+ * calls execute exactly this list.  A wire plan reports its converting
+ * kernels (PA_KERNEL_CVT_*) as ungrouped rows, one per descriptor. */
 #define PA_STAGE_PACK   0
 #define PA_STAGE_LOCAL  1
 #define PA_STAGE_UNPACK 2
@@ -322,6 +362,41 @@ pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
                                    const int64_t *sstr, int64_t soff,
                                    const int64_t *dstr, int64_t doff,
                                    int64_t scalar_size, int64_t ncomp,
+                                   const void *src, const void *dst,
+                                   int64_t out[5]);
+
+/* ---- converting copies (reduced-precision wire) ------------------------ */
+/* One strided-copy descriptor with conversion (the kernels a wire plan
+ * uses).  Strides, offsets and dims in ELEMENTS of ncomp scalars, components
+ * fastest; src holds the stored type for NARROW and ROUND and the wire type
+ * for WIDEN, dst the wire type for NARROW and the stored type otherwise.
+ * Both pointers must be aligned to their scalar; wider accesses are used only
+ * where the pointers, offsets and strides allow them. */
+pa_status pa_device_copy_wire(int nd, const int64_t *dims,
+                              const int64_t *sstr, int64_t soff,
+                              const int64_t *dstr, int64_t doff, int wire,
+                              int op, int64_t ncomp, const void *src,
+                              void *dst, void *stream);
+/* Which converting kernel runs for this descriptor (host-only; pointers are
+ * used for their alignment only).  out = {kind, V, tile_i, tile_j,
+ * sweep_depth}:
+ *  - axis 0 contiguous on both sides (1-D included): PA_KERNEL_CVT_LINEAR, a
+ *    lane moving V consecutive scalars per access.  V starts at
+ *    16 / max(src scalar bytes, dst scalar bytes) and is halved down to 1
+ *    until it divides the scalar run dims[0]*ncomp and the base pointer, the
+ *    offset and every non-unit stride of BOTH sides, in scalars;
+ *  - src contiguous along axis 0, dst along an axis ta >= 1, ncomp <= 4:
+ *    PA_KERNEL_CVT_TILE, an LDS transpose of tile_i (axis 0) x tile_j (ta)
+ *    elements holding f32 in LDS;
+ *  - otherwise PA_KERNEL_CVT_GENERIC, elementwise: correct and slow.
+ * V = 1 and tile = 0 where they do not apply; sweep_depth is 1. */
+#define PA_KERNEL_CVT_LINEAR  9
+#define PA_KERNEL_CVT_TILE    10
+#define PA_KERNEL_CVT_GENERIC 11
+pa_status pa_copy_kernel_kind_wire(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int wire, int op, int64_t ncomp,
                                    const void *src, const void *dst,
                                    int64_t out[5]);
 

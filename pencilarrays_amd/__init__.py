@@ -30,6 +30,7 @@ from .transpositions import (
     transpose_into,
     transpose_many_into,
 )
+from .wire import round_wire
 from .multiarrays import ManyPencilArray
 from .pencilio import MPIIOFile
 from . import reductions
@@ -43,7 +44,7 @@ __all__ = [
     "Topology", "dims_create", "Pencil", "PencilArray",
     "Transposition", "transpose_into", "run_transpose_sim", "ManyPencilArray",
     "MultiTransposition", "transpose_many_into", "run_transpose_sim_many",
-    "MPIIOFile", "reductions",
+    "MPIIOFile", "reductions", "round_wire",
     "gather", "gather_sim", "gather_dist",
     "CopyDesc", "TransposePlan", "build_plan", "normalize_desc",
     "identity_perm", "perm_apply", "perm_unapply", "perm_inv",

@@ -30,3 +30,27 @@ def apply_copy(desc: CopyDesc, src_flat: np.ndarray, dst_flat: np.ndarray) -> No
         strides=tuple(s * isz for s in desc.dstrides),
     )
     dv[...] = sv
+
+
+def apply_copy_conv(desc: CopyDesc, src_scalars: np.ndarray,
+                    dst_scalars: np.ndarray, ncomp: int, conv) -> None:
+    """The converting copy of a reduced-precision wire plan: ``desc`` in
+    ELEMENT units over flat SCALAR arrays of ``ncomp`` scalars per element
+    (components fastest), which may differ in dtype;
+    ``dst = conv(src)`` elementwise (wire.narrow / wire.widen / their
+    composition)."""
+    if desc.nelem == 0:
+        return
+    assert src_scalars.ndim == 1 and dst_scalars.ndim == 1
+    si, di = src_scalars.itemsize, dst_scalars.itemsize
+    sv = np.lib.stride_tricks.as_strided(
+        src_scalars[desc.soffset * ncomp:],
+        shape=tuple(desc.dims) + (ncomp,),
+        strides=tuple(s * ncomp * si for s in desc.sstrides) + (si,),
+    )
+    dv = np.lib.stride_tricks.as_strided(
+        dst_scalars[desc.doffset * ncomp:],
+        shape=tuple(desc.dims) + (ncomp,),
+        strides=tuple(s * ncomp * di for s in desc.dstrides) + (di,),
+    )
+    dv[...] = conv(sv)

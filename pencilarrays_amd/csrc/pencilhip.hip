@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pencilhip.h"
@@ -634,6 +635,234 @@ __global__ __launch_bounds__(64 * NROWS) void k_group_tile_vs(
     tile_vs_body<T, TI, TJ, NROWS, 1>(tile, (const T *)g.src, (T *)g.dst,
                                       g.d, g.ta, g.ntile_i, g.njchunk,
                                       bid - first[e]);
+}
+
+/* ---- converting kernels: reduced-precision wire ------------------------
+ *
+ * A wire pair (stored scalar -> wire scalar: f64->f32, f32->f16, f32->bf16)
+ * and an op pick the two scalar types of a converting copy: NARROW reads
+ * stored and writes wire (packs), WIDEN reads wire and writes stored
+ * (unpacks), ROUND reads and writes stored through the wire type (the fused
+ * local copy).  Conversions are round-to-nearest-even with subnormals kept
+ * (the default kernel float mode); bf16 is done on the bit pattern so the
+ * result does not depend on a library.  Descriptors stay in ELEMENT units;
+ * an element is ncomp scalars, components fastest. */
+struct bf16_t { uint16_t u; };
+
+template <typename D, typename S>
+__device__ __forceinline__ D cvt_to(S x)
+{
+    if constexpr (std::is_same<S, D>::value) {
+        return x;
+    } else if constexpr (std::is_same<D, bf16_t>::value) {
+        const uint32_t u = __float_as_uint(x);
+        bf16_t r;
+        if ((u & 0x7fffffffu) > 0x7f800000u) /* NaN stays NaN */
+            r.u = (uint16_t)((u >> 16) | 0x40u);
+        else /* RNE on the pattern; carries into the exponent up to inf */
+            r.u = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+        return r;
+    } else if constexpr (std::is_same<S, bf16_t>::value) {
+        return (D)__uint_as_float((uint32_t)x.u << 16);
+    } else {
+        return (D)x; /* v_cvt: RNE, MODE.denorm keeps subnormals */
+    }
+}
+
+template <int WIRE> struct WireT;
+template <> struct WireT<PA_WIRE_F64_F32> {
+    typedef double stored;
+    typedef float wire;
+};
+template <> struct WireT<PA_WIRE_F32_F16> {
+    typedef float stored;
+    typedef _Float16 wire;
+};
+template <> struct WireT<PA_WIRE_F32_BF16> {
+    typedef float stored;
+    typedef bf16_t wire;
+};
+
+template <int WIRE, int OP> struct CvtOp {
+    typedef typename WireT<WIRE>::stored stored;
+    typedef typename WireT<WIRE>::wire wire;
+    typedef typename std::conditional<OP == PA_WIRE_WIDEN, wire, stored>::type S;
+    typedef typename std::conditional<OP == PA_WIRE_NARROW, wire, stored>::type D;
+    static __device__ __forceinline__ D apply(S x)
+    {
+        if constexpr (OP == PA_WIRE_ROUND)
+            return cvt_to<stored>(cvt_to<wire>(x));
+        else
+            return cvt_to<D>(x);
+    }
+    /* the tile holds f32 in LDS: the wire type of f64->f32, the stored type
+     * of the 16-bit wires (no sub-dword LDS elements, which share banks) */
+    static __device__ __forceinline__ float to_lds(S x)
+    {
+        if constexpr (OP == PA_WIRE_ROUND)
+            return cvt_to<float>(cvt_to<wire>(x));
+        else
+            return cvt_to<float>(x);
+    }
+    static __device__ __forceinline__ D from_lds(float y)
+    {
+        return cvt_to<D>(y);
+    }
+};
+
+template <typename T, int V> struct alignas(sizeof(T) * V) VecT { T v[V]; };
+
+/* Linear runs with conversion: axis 0 contiguous on both sides.  The
+ * descriptor is in units of V SCALARS (the host folded ncomp into axis 0 and
+ * checked that every access of V scalars is naturally aligned on both
+ * sides); a lane converts V consecutive scalars per access. */
+template <int WIRE, int OP, int V>
+__global__ __launch_bounds__(256) void k_cvt_linear(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d)
+{
+    typedef CvtOp<WIRE, OP> C;
+    typedef VecT<typename C::S, V> SV;
+    typedef VecT<typename C::D, V> DV;
+    const SV *__restrict__ src = (const SV *)src_;
+    DV *__restrict__ dst = (DV *)dst_;
+    const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t run = d.dims[0];
+    const int64_t idx = b * blockDim.x + threadIdx.x;
+    if (idx >= d.total) return;
+    int64_t o = idx / run;
+    const int64_t i = idx - o * run;
+    int64_t so = d.soff + i, doo = d.doff + i;
+    for (int a = 1; a < d.nd; a++) {
+        const int64_t j = o % d.dims[a];
+        o /= d.dims[a];
+        so += j * d.sstr[a];
+        doo += j * d.dstr[a];
+    }
+    const SV in = src[so];
+    DV out;
+#pragma unroll
+    for (int k = 0; k < V; k++) out.v[k] = C::apply(in.v[k]);
+    dst[doo] = out;
+}
+
+/* tile of the converting transpose: CVT_TILE_TJ elements along ta, and along
+ * axis 0 as many elements as give rows of about CVT_TILE_ROW scalars (both
+ * overridable at build time for shape probes; 64 x 128 measured) */
+#ifndef CVT_TILE_TJ
+#define CVT_TILE_TJ 64
+#endif
+#ifndef CVT_TILE_ROW
+#define CVT_TILE_ROW 128
+#endif
+__host__ __device__ constexpr int cvt_tile_ti(int nc)
+{
+    return CVT_TILE_ROW / nc;
+}
+__host__ __device__ constexpr int cvt_tile_pitch(int nc)
+{
+    /* >= ti*nc and == nc modulo the 32 banks of a 4-byte LDS access, so the
+     * store phase's nc-scalar runs land on consecutive banks across the row
+     * jump (nc = 1: the classic +1 pad) */
+    return nc + ((cvt_tile_ti(nc) - 1) * nc + 31) / 32 * 32;
+}
+
+/* LDS-tiled transpose with conversion: src contiguous along axis 0, dst
+ * contiguous along axis ta, elements of NC <= 4 scalars.  Laid out like the
+ * wide-element tile: a tile row along ta is ni*NC contiguous src scalars,
+ * written to LDS at j*PITCH + q; a dst row is nj*NC contiguous scalars, lane
+ * q storing component q%NC of element q/NC from LDS j*PITCH + i*NC + q%NC.
+ * Both phases are conflict-free (see cvt_tile_pitch).  The conversion is
+ * split around the f32 LDS image: to_lds on load, from_lds on store. */
+template <int WIRE, int OP, int NC>
+__global__ __launch_bounds__(1024) void k_cvt_tile(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int ta,
+    int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+{
+    typedef CvtOp<WIRE, OP> C;
+    typedef typename C::S S;
+    typedef typename C::D D;
+    constexpr int TI = cvt_tile_ti(NC), TJ = CVT_TILE_TJ, NR = 16;
+    constexpr int PITCH = cvt_tile_pitch(NC);
+    __shared__ float tile[TJ * PITCH];
+    const S *__restrict__ src = (const S *)src_;
+    D *__restrict__ dst = (D *)dst_;
+
+    const int tx = threadIdx.x; /* 0..63 */
+    const int ty = threadIdx.y; /* 0..NR-1 */
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int64_t t_i = bid % ntile_i;
+    int64_t rest = bid / ntile_i;
+    const int64_t t_j = rest % ntile_j;
+    int64_t batch = rest / ntile_j;
+
+    int64_t so_b = d.soff, do_b = d.doff;
+    for (int a = 1; a < d.nd; a++) {
+        if (a == ta) continue;
+        const int64_t j = batch % d.dims[a];
+        batch /= d.dims[a];
+        so_b += j * d.sstr[a];
+        do_b += j * d.dstr[a];
+    }
+
+    const int64_t i0 = t_i * TI;
+    const int ni = (int)(d.dims[0] - i0 < TI ? d.dims[0] - i0 : TI);
+    const int64_t j0 = t_j * TJ;
+    const int nj = (int)(d.dims[ta] - j0 < TJ ? d.dims[ta] - j0 : TJ);
+
+    /* load: lanes sweep the scalars of one src row, rows sweep ta */
+    {
+        const int64_t sj = d.sstr[ta];
+        const S *base = src + (so_b + i0 + j0 * sj) * NC;
+        const int nw = ni * NC;
+        for (int j = ty; j < nj; j += NR) {
+            const S *row = base + (int64_t)j * sj * NC;
+            float *trow = tile + j * PITCH;
+            for (int q = tx; q < nw; q += 64) trow[q] = C::to_lds(row[q]);
+        }
+    }
+    __syncthreads();
+    /* store: lanes sweep the scalars of one dst row, rows sweep axis 0 */
+    {
+        const int64_t di = d.dstr[0];
+        D *base = dst + (do_b + j0 + i0 * di) * NC;
+        const int nw = nj * NC;
+        for (int i = ty; i < ni; i += NR) {
+            D *row = base + (int64_t)i * di * NC;
+            const float *tcol = tile + i * NC;
+            for (int q = tx; q < nw; q += 64) {
+                const int j = q / NC;
+                row[q] = C::from_lds(tcol[q + j * (PITCH - NC)]);
+            }
+        }
+    }
+}
+
+/* Elementwise converting fallback: descriptors with no contiguous axis, and
+ * transposable ones with more than 4 components.  Correct and slow. */
+template <int WIRE, int OP>
+__global__ __launch_bounds__(256) void k_cvt_generic(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int nc)
+{
+    typedef CvtOp<WIRE, OP> C;
+    const typename C::S *__restrict__ src = (const typename C::S *)src_;
+    typename C::D *__restrict__ dst = (typename C::D *)dst_;
+    int64_t idx = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) *
+                      blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * gridDim.y * blockDim.x;
+    const int64_t nscal = d.total * nc;
+    for (; idx < nscal; idx += stride) {
+        int64_t rem = idx / nc;
+        const int64_t c = idx - rem * nc;
+        int64_t so = d.soff, doo = d.doff;
+        for (int a = 0; a < d.nd; a++) {
+            const int64_t j = rem % d.dims[a];
+            rem /= d.dims[a];
+            so += j * d.sstr[a];
+            doo += j * d.dstr[a];
+        }
+        dst[doo * nc + c] = C::apply(src[so * nc + c]);
+    }
 }
 
 /* ================= descriptor normalization & dispatch ============= */
@@ -1285,6 +1514,237 @@ static pa_status launch_desc(const CopyDescH &dn, int64_t ssz, int64_t ncomp,
     return launch_sel(k, src, dst, stream);
 }
 
+/* ---- reduced-precision wire: selection and launch ---------------------- */
+
+/* The decision for a converting copy, made in ONE place like select_kernel():
+ * launch_cvt_sel() executes it, pa_copy_kernel_kind_wire() reports it. */
+struct CvtSel {
+    int kind = PA_KERNEL_NONE;
+    int wire = 0, op = 0, ncomp = 1;
+    int V = 1;          /* scalars per access (linear) */
+    int ti = 0, tj = 0; /* tile shape in elements (tile) */
+    int ta = -1;        /* dst-contiguous axis (tile) */
+    CopyDescH d;        /* linear: in units of V scalars; else elements */
+};
+
+#define PA_CVT_TILE_MAX_COMP 4
+
+/* stored / wire scalar bytes of a wire pair; false for an unknown code */
+static bool wire_sizes(int wire, int64_t *stored, int64_t *wsz)
+{
+    switch (wire) {
+    case PA_WIRE_F64_F32: *stored = 8; *wsz = 4; return true;
+    case PA_WIRE_F32_F16:
+    case PA_WIRE_F32_BF16: *stored = 4; *wsz = 2; return true;
+    default: return false;
+    }
+}
+
+static pa_status check_wire(int wire, int op, int64_t ncomp)
+{
+    int64_t a, b;
+    if (!wire_sizes(wire, &a, &b)) return fail("unknown wire pair %d", wire);
+    if (op != PA_WIRE_NARROW && op != PA_WIRE_WIDEN && op != PA_WIRE_ROUND)
+        return fail("unknown wire op %d", op);
+    if (ncomp < 1) return fail("invalid ncomp %lld", (long long)ncomp);
+    return 0;
+}
+
+static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
+                                   int64_t ncomp, const void *src,
+                                   const void *dst, CvtSel *out)
+{
+    if (pa_status st = check_wire(wire, op, ncomp)) return st;
+    *out = CvtSel();
+    out->wire = wire;
+    out->op = op;
+    out->ncomp = (int)ncomp;
+    if (dn.total == 0) return 0;
+    int64_t stored, wsz;
+    wire_sizes(wire, &stored, &wsz);
+    const int64_t ssz = op == PA_WIRE_WIDEN ? wsz : stored;
+    const int64_t dsz = op == PA_WIRE_NARROW ? wsz : stored;
+
+    if (dn.sstr[0] == 1 && dn.dstr[0] == 1) {
+        /* scalar units: the components join the contiguous axis */
+        CopyDescH w = dn;
+        w.dims[0] *= ncomp;
+        w.soff *= ncomp;
+        w.doff *= ncomp;
+        for (int a = 1; a < w.nd; a++) {
+            w.sstr[a] *= ncomp;
+            w.dstr[a] *= ncomp;
+        }
+        /* V scalars per access, each access naturally aligned on both
+         * sides: V divides the run, both offsets, every non-unit stride and
+         * (in scalars) both base addresses */
+        int64_t V = 16 / std::max(ssz, dsz);
+        auto ok = [&](int64_t v) {
+            if (w.dims[0] % v || w.soff % v || w.doff % v) return false;
+            if ((uintptr_t)src % (uintptr_t)(v * ssz)) return false;
+            if ((uintptr_t)dst % (uintptr_t)(v * dsz)) return false;
+            for (int a = 1; a < w.nd; a++)
+                if (w.sstr[a] % v || w.dstr[a] % v) return false;
+            return true;
+        };
+        while (V > 1 && !ok(V)) V >>= 1;
+        w.dims[0] /= V;
+        w.soff /= V;
+        w.doff /= V;
+        for (int a = 1; a < w.nd; a++) {
+            w.sstr[a] /= V;
+            w.dstr[a] /= V;
+        }
+        w.total = 1;
+        for (int a = 0; a < w.nd; a++) w.total *= w.dims[a];
+        out->kind = PA_KERNEL_CVT_LINEAR;
+        out->V = (int)V;
+        out->d = w;
+        return 0;
+    }
+
+    out->d = dn;
+    int ta = -1;
+    if (dn.sstr[0] == 1)
+        for (int a = 1; a < dn.nd; a++)
+            if (dn.dstr[a] == 1) { ta = a; break; }
+    if (ta > 0 && ncomp <= PA_CVT_TILE_MAX_COMP) {
+        out->kind = PA_KERNEL_CVT_TILE;
+        out->ta = ta;
+        out->ti = cvt_tile_ti((int)ncomp);
+        out->tj = CVT_TILE_TJ;
+        return 0;
+    }
+    out->kind = PA_KERNEL_CVT_GENERIC;
+    return 0;
+}
+
+/* workgroups of a converting selection: the grid launch_cvt_sel() launches */
+static int64_t cvt_grid(const CvtSel &k, int64_t *nti, int64_t *ntj)
+{
+    const CopyDescH &w = k.d;
+    *nti = *ntj = 0;
+    switch (k.kind) {
+    case PA_KERNEL_CVT_LINEAR:
+        return grid_exact(w.total, 256);
+    case PA_KERNEL_CVT_GENERIC:
+        return grid_for(w.total * k.ncomp, 256);
+    case PA_KERNEL_CVT_TILE: {
+        int64_t nbatch = 1;
+        for (int a = 1; a < w.nd; a++)
+            if (a != k.ta) nbatch *= w.dims[a];
+        *nti = (w.dims[0] + k.ti - 1) / k.ti;
+        *ntj = (w.dims[k.ta] + k.tj - 1) / k.tj;
+        return *nti * *ntj * nbatch;
+    }
+    default:
+        return 0;
+    }
+}
+
+/* expand F(WIRE, OP) for the runtime pair (wire, op) */
+#define CVT_FOR_WIRE_OP(wire, op, F)                                         \
+    switch ((wire) * 3 + (op)) {                                             \
+    case 3: F(1, 0); break;                                                  \
+    case 4: F(1, 1); break;                                                  \
+    case 5: F(1, 2); break;                                                  \
+    case 6: F(2, 0); break;                                                  \
+    case 7: F(2, 1); break;                                                  \
+    case 8: F(2, 2); break;                                                  \
+    case 9: F(3, 0); break;                                                  \
+    case 10: F(3, 1); break;                                                 \
+    case 11: F(3, 2); break;                                                 \
+    default: return fail("bad wire pair %d / op %d", (wire), (op));          \
+    }
+
+/* V starts at 16 / (widest scalar): 4 only exists for the f32 pairs */
+template <int W, int O>
+static void launch_cvt_linear(int V, dim3 grid, hipStream_t stream,
+                              const void *src, void *dst, const DescDev &dd)
+{
+    if constexpr (W != PA_WIRE_F64_F32) {
+        if (V == 4) {
+            hipLaunchKernelGGL((k_cvt_linear<W, O, 4>), grid, dim3(256), 0,
+                               stream, src, dst, dd);
+            return;
+        }
+    }
+    if (V == 2)
+        hipLaunchKernelGGL((k_cvt_linear<W, O, 2>), grid, dim3(256), 0,
+                           stream, src, dst, dd);
+    else
+        hipLaunchKernelGGL((k_cvt_linear<W, O, 1>), grid, dim3(256), 0,
+                           stream, src, dst, dd);
+}
+
+static pa_status launch_cvt_sel(const CvtSel &k, const void *src, void *dst,
+                                hipStream_t stream)
+{
+    if (k.kind == PA_KERNEL_NONE) return 0;
+    int64_t nti, ntj;
+    const int64_t nblocks = cvt_grid(k, &nti, &ntj);
+    DescDev dd = to_dev(k.d);
+    dim3 grid;
+    switch (k.kind) {
+    case PA_KERNEL_CVT_LINEAR: {
+        if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
+        if (k.V != 1 && k.V != 2 && !(k.V == 4 && k.wire != PA_WIRE_F64_F32))
+            return fail("bad vector width %d", k.V);
+#define CVT_LIN(W, O) launch_cvt_linear<W, O>(k.V, grid, stream, src, dst, dd)
+        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_LIN)
+#undef CVT_LIN
+        break;
+    }
+    case PA_KERNEL_CVT_TILE: {
+        if (k.ta < 1 || k.ncomp > PA_CVT_TILE_MAX_COMP ||
+            k.ti != cvt_tile_ti(k.ncomp) || k.tj != CVT_TILE_TJ)
+            return fail("bad converting-tile selection");
+        if (pa_status gst = grid2d(nblocks, 64 * 16, &grid)) return gst;
+#define CVT_TILE_NC(W, O, NC)                                                \
+    hipLaunchKernelGGL((k_cvt_tile<W, O, NC>), grid, dim3(64, 16), 0,        \
+                       stream, src, dst, dd, k.ta, nti, ntj, nblocks)
+#define CVT_TILE(W, O)                                                       \
+    do {                                                                     \
+        if (k.ncomp == 1)                                                    \
+            CVT_TILE_NC(W, O, 1);                                            \
+        else if (k.ncomp == 2)                                               \
+            CVT_TILE_NC(W, O, 2);                                            \
+        else if (k.ncomp == 3)                                               \
+            CVT_TILE_NC(W, O, 3);                                            \
+        else                                                                 \
+            CVT_TILE_NC(W, O, 4);                                            \
+    } while (0)
+        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_TILE)
+#undef CVT_TILE
+#undef CVT_TILE_NC
+        break;
+    }
+    case PA_KERNEL_CVT_GENERIC: {
+        grid = dim3((uint32_t)nblocks); /* grid-stride kernel */
+#define CVT_GEN(W, O)                                                        \
+    hipLaunchKernelGGL((k_cvt_generic<W, O>), grid, dim3(256), 0, stream,    \
+                       src, dst, dd, k.ncomp)
+        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_GEN)
+#undef CVT_GEN
+        break;
+    }
+    default:
+        return fail("bad converting kernel kind %d", k.kind);
+    }
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static pa_status launch_desc_cvt(const CopyDescH &dn, int wire, int op,
+                                 int64_t ncomp, const void *src, void *dst,
+                                 hipStream_t stream)
+{
+    CvtSel k;
+    pa_status st = select_kernel_cvt(dn, wire, op, ncomp, src, dst, &k);
+    if (st) return st;
+    return launch_cvt_sel(k, src, dst, stream);
+}
+
 /* ================= metadata ======================================== */
 
 struct Range { int64_t lo, hi; };
@@ -1392,6 +1852,11 @@ struct pa_plan {
     int64_t esz;   /* bytes per element = ssz * ncomp */
     int64_t ssz;   /* bytes per scalar */
     int64_t ncomp; /* scalars per element, components fastest */
+    /* reduced-precision wire (pa_plan_create_wire): the pair code, or 0.
+     * Staging buffers and messages hold elements of msg_esz bytes — esz for
+     * an ordinary plan, (wire scalar bytes) * ncomp for a wire plan. */
+    int wire = 0;
+    int64_t msg_esz;
     int R;    /* -1 = same decomposition */
     int P;    /* subgroup size */
     int myk;  /* my coordinate along R */
@@ -1435,6 +1900,16 @@ struct pa_plan {
 };
 
 static void free_stage_tables(pa_plan *p);
+
+/* one descriptor of a plan: the ordinary copy, or on a wire plan the
+ * converting copy with the op its stage calls for (op is ignored otherwise) */
+static pa_status plan_launch(const pa_plan *p, int op, const CopyDescH &d,
+                             const void *src, void *dst, hipStream_t stream)
+{
+    if (p->wire)
+        return launch_desc_cvt(d, p->wire, op, p->ncomp, src, dst, stream);
+    return launch_desc(d, p->ssz, p->ncomp, src, dst, stream);
+}
 
 static int64_t prod_extra(const pa_plan &pl)
 {
@@ -1816,6 +2291,7 @@ pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
     pl->esz = scalar_size * ncomp;
     pl->ssz = scalar_size;
     pl->ncomp = ncomp;
+    pl->msg_esz = pl->esz;
     pl->R = R;
     pl->aliased = (flags & 1) != 0;
     if (const char *ce = getenv("PENCILHIP_EXCHANGE_CHUNKS")) {
@@ -1965,6 +2441,29 @@ pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
     return 0;
 }
 
+pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
+                              int wire, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              pa_plan **out)
+{
+    if (!out) return fail("null plan output");
+    if (pa_status st = check_wire(wire, PA_WIRE_NARROW, ncomp)) return st;
+    int64_t stored, wsz;
+    wire_sizes(wire, &stored, &wsz);
+    /* the same tables as the plan of the stored type; only byte sizes differ */
+    pa_plan *pl = nullptr;
+    if (pa_status st = pa_plan_create_comp(pin, pout, stored, ncomp, e,
+                                           extra_dims, rank, flags, &pl))
+        return st;
+    pl->wire = wire;
+    pl->msg_esz = wsz * ncomp;
+    pl->chunks = 1; /* the exchange of a wire plan is always a single group */
+    *out = pl;
+    return 0;
+}
+
+int pa_plan_wire(const pa_plan *p) { return p ? p->wire : 0; }
+
 void pa_plan_destroy(pa_plan *p)
 {
     if (!p) return;
@@ -1998,8 +2497,8 @@ pa_status pa_plan_set_comm(pa_plan *p, pa_comm *c)
 pa_status pa_plan_buffer_sizes(const pa_plan *p, int64_t *send_bytes,
                                int64_t *recv_bytes)
 {
-    *send_bytes = p->send_total * p->esz;
-    *recv_bytes = p->recv_total * p->esz;
+    *send_bytes = p->send_total * p->msg_esz;
+    *recv_bytes = p->recv_total * p->msg_esz;
     return 0;
 }
 
@@ -2024,9 +2523,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
     const bool need_bufs = p->send_total > 0 || p->recv_total > 0;
     if (need_bufs && !p->send_buf && !p->own_bufs) {
         if (p->send_total)
-            HIP_CHECK(hipMalloc(&p->send_buf, p->send_total * p->esz));
+            HIP_CHECK(hipMalloc(&p->send_buf, p->send_total * p->msg_esz));
         if (p->recv_total)
-            HIP_CHECK(hipMalloc(&p->recv_buf, p->recv_total * p->esz));
+            HIP_CHECK(hipMalloc(&p->recv_buf, p->recv_total * p->msg_esz));
         p->own_bufs = true;
     }
 
@@ -2050,12 +2549,12 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
     for (auto &blk : p->peers)
         if (blk.has_pack) {
             pa_status st =
-                launch_desc(blk.pack, p->ssz, p->ncomp, src_parent,
+                plan_launch(p, PA_WIRE_NARROW, blk.pack, src_parent,
                             p->send_buf, stream);
             if (st) return st;
         }
     if (p->has_self) {
-        pa_status st = launch_desc(p->self_pack, p->ssz, p->ncomp,
+        pa_status st = plan_launch(p, PA_WIRE_NARROW, p->self_pack,
                                    src_parent, p->recv_buf, stream);
         if (st) return st;
     }
@@ -2110,8 +2609,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
                         NCCL_CHECK(ncclRecv(
                             (char *)p->recv_buf +
                                 (blk.recv_off + lo * blk.recv_rowelems) *
-                                    p->esz,
-                            (size_t)((hi - lo) * blk.recv_rowelems * p->esz),
+                                    p->msg_esz,
+                            (size_t)((hi - lo) * blk.recv_rowelems *
+                                     p->msg_esz),
                             ncclUint8, blk.k, p->comm->comm, p->comm_stream));
                 }
                 if (blk.send_n) {
@@ -2121,8 +2621,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
                         NCCL_CHECK(ncclSend(
                             (const char *)p->send_buf +
                                 (blk.send_off + lo * blk.send_rowelems) *
-                                    p->esz,
-                            (size_t)((hi - lo) * blk.send_rowelems * p->esz),
+                                    p->msg_esz,
+                            (size_t)((hi - lo) * blk.send_rowelems *
+                                     p->msg_esz),
                             ncclUint8, blk.k, p->comm->comm, p->comm_stream));
                 }
             }
@@ -2137,12 +2638,12 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
      * exchange (aliased mode: unpack the staged self block instead) */
     if (p->has_local) {
         pa_status st =
-            launch_desc(p->local, p->ssz, p->ncomp, src_parent, dst_parent,
+            plan_launch(p, PA_WIRE_ROUND, p->local, src_parent, dst_parent,
                         stream);
         if (st) return st;
     }
     if (p->has_self) {
-        pa_status st = launch_desc(p->self_unpack, p->ssz, p->ncomp,
+        pa_status st = plan_launch(p, PA_WIRE_WIDEN, p->self_unpack,
                                    p->recv_buf, dst_parent, stream);
         if (st) return st;
     }
@@ -2158,7 +2659,7 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
         for (auto &blk : p->peers)
             if (blk.has_unpack) {
                 pa_status st =
-                    launch_desc(blk.unpack, p->ssz, p->ncomp, p->recv_buf,
+                    plan_launch(p, PA_WIRE_WIDEN, blk.unpack, p->recv_buf,
                                 dst_parent, stream);
                 if (st) return st;
             }
@@ -2174,7 +2675,7 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
                 if (hi <= lo) continue;
                 CopyDescH d = chunk_of_raw(blk.unpack_raw, lo, hi);
                 pa_status st =
-                    launch_desc(d, p->ssz, p->ncomp, p->recv_buf, dst_parent,
+                    plan_launch(p, PA_WIRE_WIDEN, d, p->recv_buf, dst_parent,
                                 stream);
                 if (st) return st;
             }
@@ -2359,6 +2860,41 @@ pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
     return 0;
 }
 
+pa_status pa_device_copy_wire(int nd, const int64_t *dims,
+                              const int64_t *sstr, int64_t soff,
+                              const int64_t *dstr, int64_t doff, int wire,
+                              int op, int64_t ncomp, const void *src,
+                              void *dst, void *stream)
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_wire(wire, op, ncomp)) return st;
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    return launch_desc_cvt(d, wire, op, ncomp, src, dst,
+                           (hipStream_t)stream);
+}
+
+pa_status pa_copy_kernel_kind_wire(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int wire, int op, int64_t ncomp,
+                                   const void *src, const void *dst,
+                                   int64_t out[5])
+{
+    if (!out) return fail("null output");
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_wire(wire, op, ncomp)) return st;
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    CvtSel k;
+    if (pa_status st = select_kernel_cvt(d, wire, op, ncomp, src, dst, &k))
+        return st;
+    out[0] = k.kind;
+    out[1] = k.V;
+    out[2] = k.ti;
+    out[3] = k.tj;
+    out[4] = 1; /* the converting tile sweeps one tile per workgroup */
+    return 0;
+}
+
 } /* extern "C" */
 
 /* ================= multi-field transposes ========================== */
@@ -2425,6 +2961,8 @@ static pa_status many_desc(const pa_plan *p, int n, int f, int which, int k,
 
 struct StageItem {
     KernelSel k;
+    bool cvt = false; /* wire plan: the converting selection c runs, not k */
+    CvtSel c;
     const void *src;
     void *dst;
     int64_t nti = 0, njc = 0, nblocks = 0;
@@ -2519,11 +3057,32 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         CopyDescH d;
         if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
         StageItem it;
+        it.src = src;
+        it.dst = dst;
+        if (p->wire) {
+            /* converting kernels: ungrouped rows, one launch per entry */
+            const int op = which == 0 ? PA_WIRE_ROUND
+                           : (which == 1 || which == 3) ? PA_WIRE_NARROW
+                                                        : PA_WIRE_WIDEN;
+            it.cvt = true;
+            if (pa_status st = select_kernel_cvt(d, p->wire, op, p->ncomp,
+                                                 src, dst, &it.c))
+                return st;
+            it.nblocks = cvt_grid(it.c, &it.nti, &it.njc);
+            if (it.nblocks == 0) return 0;
+            StageLaunch l;
+            l.kind = it.c.kind;
+            l.word = 0;
+            l.grouped = false;
+            l.items.push_back((int)t->items.size());
+            l.nblocks = it.nblocks;
+            t->items.push_back(it);
+            t->launches.push_back(l);
+            return 0;
+        }
         if (pa_status st =
                 select_kernel_comp(d, p->ssz, p->ncomp, src, dst, &it.k))
             return st;
-        it.src = src;
-        it.dst = dst;
         sel_grid(it.k, &it);
         if (it.nblocks == 0) return 0; /* empty: contributes no blocks */
         int sig = 0;
@@ -2748,7 +3307,8 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
             st = launch_group(l, stream);
         else {
             const StageItem &it = t->items[l.items[0]];
-            st = launch_sel(it.k, it.src, it.dst, stream);
+            st = it.cvt ? launch_cvt_sel(it.c, it.src, it.dst, stream)
+                        : launch_sel(it.k, it.src, it.dst, stream);
         }
         if (st) return st;
     }
@@ -2762,8 +3322,8 @@ pa_status pa_plan_buffer_sizes_many(const pa_plan *p, int n,
 {
     if (!p || !send_bytes || !recv_bytes) return fail("null argument");
     if (n < 1) return fail("n must be >= 1 (got %d)", n);
-    *send_bytes = (int64_t)n * p->send_total * p->esz;
-    *recv_bytes = (int64_t)n * p->recv_total * p->esz;
+    *send_bytes = (int64_t)n * p->send_total * p->msg_esz;
+    *recv_bytes = (int64_t)n * p->recv_total * p->msg_esz;
     return 0;
 }
 
@@ -2778,10 +3338,10 @@ pa_status pa_plan_peer_message(const pa_plan *p, int n, int k, int64_t out[4])
         out[0] = out[1] = out[2] = out[3] = 0;
         return 0;
     }
-    out[0] = (int64_t)n * b.send_off * p->esz;
-    out[1] = (int64_t)n * b.send_n * p->esz;
-    out[2] = (int64_t)n * b.recv_off * p->esz;
-    out[3] = (int64_t)n * b.recv_n * p->esz;
+    out[0] = (int64_t)n * b.send_off * p->msg_esz;
+    out[1] = (int64_t)n * b.send_n * p->msg_esz;
+    out[2] = (int64_t)n * b.recv_off * p->msg_esz;
+    out[3] = (int64_t)n * b.recv_n * p->msg_esz;
     return 0;
 }
 

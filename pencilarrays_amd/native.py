@@ -63,13 +63,34 @@ KERNEL_TILE_VS = 5
 KERNEL_TILE_PK = 6
 KERNEL_GENERIC = 7
 KERNEL_TILE_WIDE = 8
+# converting kernels of a reduced-precision wire (pa_copy_kernel_kind_wire)
+KERNEL_CVT_LINEAR = 9
+KERNEL_CVT_TILE = 10
+KERNEL_CVT_GENERIC = 11
 KERNEL_NAMES = {
     KERNEL_NONE: "NONE", KERNEL_COPY_1D: "COPY_1D",
     KERNEL_COPY_1D_NT: "COPY_1D_NT", KERNEL_LINEAR: "LINEAR",
     KERNEL_TILE: "TILE", KERNEL_TILE_VS: "TILE_VS",
     KERNEL_TILE_PK: "TILE_PK", KERNEL_GENERIC: "GENERIC",
-    KERNEL_TILE_WIDE: "TILE_WIDE",
+    KERNEL_TILE_WIDE: "TILE_WIDE", KERNEL_CVT_LINEAR: "CVT_LINEAR",
+    KERNEL_CVT_TILE: "CVT_TILE", KERNEL_CVT_GENERIC: "CVT_GENERIC",
 }
+
+# wire pairs (stored -> wire) and ops of a converting copy
+WIRE_F64_F32, WIRE_F32_F16, WIRE_F32_BF16 = 1, 2, 3
+WIRE_NARROW, WIRE_WIDEN, WIRE_ROUND = 0, 1, 2
+WIRE_STORED_BYTES = {WIRE_F64_F32: 8, WIRE_F32_F16: 4, WIRE_F32_BF16: 4}
+WIRE_BYTES = {WIRE_F64_F32: 4, WIRE_F32_F16: 2, WIRE_F32_BF16: 2}
+
+
+class WireKernelKind(NamedTuple):
+    """pa_copy_kernel_kind_wire: ``vec`` scalars per access (linear),
+    ``tile_i`` x ``tile_j`` elements per workgroup (tile)."""
+    kind: int
+    vec: int
+    tile_i: int
+    tile_j: int
+    sweep_depth: int
 
 
 class KernelKind(NamedTuple):
@@ -149,15 +170,48 @@ def device_copy(desc, esz: int, src_ptr: int, dst_ptr: int,
                "pa_device_copy_comp")
 
 
+def copy_kernel_kind_wire(desc, wire: int, op: int, ncomp: int = 1,
+                          src_ptr: int = 0,
+                          dst_ptr: int = 0) -> WireKernelKind:
+    """Which converting kernel ``pa_device_copy_wire`` / a wire plan launches
+    for ``desc`` (element units, ``ncomp`` scalars per element); host-only,
+    the pointers are used for their alignment only."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    out = (I64 * 5)()
+    _check(lib, lib.pa_copy_kernel_kind_wire(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), int(wire), int(op), I64(ncomp),
+        VP(src_ptr), VP(dst_ptr), out), "pa_copy_kernel_kind_wire")
+    return WireKernelKind(*(int(v) for v in out))
+
+
+def device_copy_wire(desc, wire: int, op: int, ncomp: int, src_ptr: int,
+                     dst_ptr: int, stream: int = 0) -> None:
+    """Run one converting strided copy on the device
+    (pa_device_copy_wire)."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    _check(lib, lib.pa_device_copy_wire(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), int(wire), int(op), I64(ncomp),
+        VP(src_ptr), VP(dst_ptr), VP(stream)), "pa_device_copy_wire")
+
+
 class NativePlan:
     """pa_plan plus the pa_topology/pa_pencil handles it needs.  Plan
     building is host-only (works without a GPU); execute needs one."""
 
     def __init__(self, Pi, Po, rank: int, elem_size: int,
                  extra_dims: Tuple[int, ...] = (), aliased: bool = False,
-                 ncomp: int = 1):
+                 ncomp: int = 1, wire: Optional[int] = None):
         """``ncomp > 1``: elements of ``ncomp`` scalars of ``elem_size``
-        bytes, components fastest (pa_plan_create_comp)."""
+        bytes, components fastest (pa_plan_create_comp).  ``wire``: a wire
+        pair code (WIRE_F64_F32, ...) for a reduced-precision wire plan
+        (pa_plan_create_wire); ``elem_size`` is then the stored scalar
+        size."""
         lib = self.lib = load()
         topo = Pi.topology
         # both pa_pencils are built against ONE pa_topology handle, so the
@@ -186,14 +240,31 @@ class NativePlan:
         self._plan = VP()
         e = len(extra_dims)
         self.ncomp = int(ncomp)
-        _check(lib, lib.pa_plan_create_comp(
-            self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
-            (I64 * e)(*extra_dims) if e else None, rank,
-            1 if aliased else 0,
-            ctypes.byref(self._plan)), "pa_plan_create_comp")
+        self.wire = wire
+        if wire is None:
+            _check(lib, lib.pa_plan_create_comp(
+                self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
+                (I64 * e)(*extra_dims) if e else None, rank,
+                1 if aliased else 0,
+                ctypes.byref(self._plan)), "pa_plan_create_comp")
+        else:
+            if WIRE_STORED_BYTES.get(wire, elem_size) != elem_size:
+                raise ValueError(
+                    f"wire pair {wire} stores {WIRE_STORED_BYTES[wire]}-byte "
+                    f"scalars, not {elem_size}")
+            _check(lib, lib.pa_plan_create_wire(
+                self._pi, self._po, int(wire), I64(self.ncomp), e,
+                (I64 * e)(*extra_dims) if e else None, rank,
+                1 if aliased else 0,
+                ctypes.byref(self._plan)), "pa_plan_create_wire")
         self.nproc_sub = lib.pa_plan_nproc_sub(self._plan)
         self.r_dim = lib.pa_plan_r_dim(self._plan)
         self.my_k = lib.pa_plan_my_k(self._plan)
+
+    def plan_wire(self) -> int:
+        """The plan's wire pair code, 0 for an ordinary plan
+        (pa_plan_wire)."""
+        return int(self.lib.pa_plan_wire(self._plan))
 
     def buffer_sizes(self) -> Tuple[int, int]:
         s, r = I64(), I64()
@@ -528,6 +599,18 @@ def staging_pool(device) -> StagingPool:
     return _POOLS[idx]
 
 
+def _native_plan_for(plan, src, pair) -> NativePlan:
+    """The native plan of a (Multi)Transposition over arrays like ``src``;
+    ``pair`` is its wire.WirePair or None."""
+    if pair is None:
+        return NativePlan(plan.Pi, plan.Po, plan.rank,
+                          src.data.element_size(), plan.extra_dims,
+                          aliased=plan.aliased, ncomp=src.ncomp)
+    return NativePlan(plan.Pi, plan.Po, plan.rank, pair.stored.itemsize,
+                      plan.extra_dims, aliased=plan.aliased,
+                      ncomp=src.ncomp * pair.comps, wire=pair.code)
+
+
 class NativeTransposition:
     """GPU execution of one Transposition: staging buffers from torch's
     allocator, kernels + RCCL inside the native library."""
@@ -537,11 +620,8 @@ class NativeTransposition:
         self.torch = torch
         plan = t.plan
         src = t.src
-        esz = src.data.element_size()
         self.np_plan = plan
-        self.native = NativePlan(plan.Pi, plan.Po, plan.rank, esz,
-                                 plan.extra_dims, aliased=plan.aliased,
-                                 ncomp=src.ncomp)
+        self.native = _native_plan_for(plan, src, getattr(t, "wire", None))
         sb, rb = self.native.buffer_sizes()
         dev = src.data.device
         # Staging comes from the per-device shared pool (the reference's
@@ -599,9 +679,7 @@ class NativeMultiTransposition:
         plan = mt.plan
         src = mt.srcs[0]
         self.n = len(mt.srcs)
-        self.native = NativePlan(plan.Pi, plan.Po, plan.rank,
-                                 src.data.element_size(), plan.extra_dims,
-                                 aliased=plan.aliased, ncomp=src.ncomp)
+        self.native = _native_plan_for(plan, src, getattr(mt, "wire", None))
         sb, rb = self.native.buffer_sizes_many(self.n)
         dev = src.data.device
         self._need = (max(sb, 1), max(rb, 1))

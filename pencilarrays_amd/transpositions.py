@@ -25,10 +25,11 @@ from typing import Sequence
 import numpy as np
 
 from .array import PencilArray
-from .copyexec import apply_copy
+from .copyexec import apply_copy, apply_copy_conv
 from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
                    copydesc_many, peer_message)
+from .wire import narrow, resolve_wire, widen
 
 MPI_TAG = 42  # Transpositions.jl:469
 
@@ -40,6 +41,25 @@ def _wire(buf: np.ndarray):
     if buf.dtype.kind == "V":
         buf = buf.view(np.uint8)
     return torch.from_numpy(buf)
+
+
+def _wire_pair(dest: PencilArray, src: PencilArray, wire_dtype):
+    """The wire pair of a transpose ``dest <- src`` sent as ``wire_dtype``
+    (ValueError where the engine has none), or None."""
+    if wire_dtype is None:
+        return None
+    pair = resolve_wire(src.data.dtype, wire_dtype)
+    if str(dest.data.dtype) != str(src.data.dtype):
+        raise ValueError(
+            f"a reduced-precision wire needs dest and src of one dtype: "
+            f"{dest.data.dtype} != {src.data.dtype}")
+    return pair
+
+
+def _wire_convs(pair):
+    """(narrow, widen, round) of a wire pair as elementwise functions."""
+    return (lambda x: narrow(x, pair), lambda w: widen(w, pair),
+            lambda x: widen(narrow(x, pair), pair))
 
 
 def _arrays_alias(a, b) -> bool:
@@ -63,8 +83,15 @@ def _arrays_alias(a, b) -> bool:
 
 class Transposition:
     def __init__(self, dest: PencilArray, src: PencilArray,
-                 method: str = "grouped"):
+                 method: str = "grouped", wire_dtype=None):
         """``Transposition(Ao, Ai; method)`` (Transpositions.jl:94-119).
+
+        ``wire_dtype`` (``"float32"``, ``"float16"``, ``"bfloat16"``, or the
+        numpy / torch dtype) sends the data in that narrower real scalar type:
+        packs narrow, unpacks widen, the local copy rounds, so that
+        ``dest == T(round_wire(src))`` whatever the process grid
+        (pa_plan_create_wire).  complex128 with float32 is complex64 on the
+        wire.  ``None`` moves the bytes as they are.
 
         ``method`` is accepted for signature parity with the reference's
         PointToPoint/Alltoallv choice (:56-68): on MI355X both map to the
@@ -86,6 +113,7 @@ class Transposition:
         if method not in ("grouped", "point_to_point", "alltoallv"):
             raise ValueError(f"unknown transpose method {method!r}")
         self.method = method
+        self.wire = _wire_pair(dest, src, wire_dtype)
         self.src = src
         self.dest = dest
         self.aliased = _arrays_alias(src.data, dest.data)
@@ -99,6 +127,8 @@ class Transposition:
     # ------------------------------------------------------------------
 
     def _execute_numpy(self, use_dist: bool):
+        if self.wire is not None:
+            return self._execute_numpy_wire(use_dist)
         plan = self.plan
         # vector-valued elements: one opaque B-byte item per element, so the
         # element-unit descriptors apply unchanged
@@ -175,6 +205,71 @@ class Transposition:
             if blk.unpack is not None:
                 apply_copy(blk.unpack, recv_buf, dst_flat)
 
+    def _execute_numpy_wire(self, use_dist: bool):
+        """The same stages with a reduced-precision wire: staging buffers of
+        the wire type, packs narrow, unpacks widen, the local copy rounds."""
+        plan, pair = self.plan, self.wire
+        nc = self.src.ncomp * pair.comps  # stored scalars per element
+        src = self.src.data.view(pair.stored)
+        dst = self.dest.data.view(pair.stored)
+        nar, wid, rnd = _wire_convs(pair)
+        send_buf = np.empty(plan.send_nelem_total * nc, dtype=pair.carrier)
+        recv_buf = np.empty(plan.recv_nelem_total * nc, dtype=pair.carrier)
+        exchanging = plan.r_dim is not None and plan.nproc_sub > 1
+
+        for blk in plan.peers:
+            if blk.pack is not None:
+                apply_copy_conv(blk.pack, src, send_buf, nc, nar)
+        if plan.self_pack is not None:
+            apply_copy_conv(plan.self_pack, src, recv_buf, nc, nar)
+
+        reqs = []
+        if exchanging:
+            if not use_dist:
+                raise RuntimeError(
+                    "distributed transpose requires torch.distributed to be "
+                    "initialised (or use run_transpose_sim for in-process "
+                    "tests)")
+            import torch
+            import torch.distributed as dist
+            topo = plan.Pi.topology
+            if dist.get_world_size() != topo.nranks:
+                raise RuntimeError(
+                    f"torch.distributed world size {dist.get_world_size()} "
+                    f"!= topology nranks {topo.nranks}")
+            if dist.get_rank() != plan.rank:
+                raise RuntimeError(
+                    f"torch.distributed rank {dist.get_rank()} != topology "
+                    f"rank {plan.rank}")
+            for blk in plan.peers:
+                if blk.peer_k == plan.my_k:
+                    continue
+                # the wire-typed slices travel as their bytes
+                if blk.recv_nelem > 0:
+                    rt = torch.from_numpy(recv_buf[
+                        blk.recv_offset * nc:
+                        (blk.recv_offset + blk.recv_nelem) * nc
+                    ].view(np.uint8))
+                    reqs.append(dist.irecv(rt, src=blk.global_rank,
+                                           tag=MPI_TAG))
+                if blk.send_nelem > 0:
+                    st = torch.from_numpy(send_buf[
+                        blk.send_offset * nc:
+                        (blk.send_offset + blk.send_nelem) * nc
+                    ].view(np.uint8))
+                    reqs.append(dist.isend(st, dst=blk.global_rank,
+                                           tag=MPI_TAG))
+
+        if plan.local is not None:
+            apply_copy_conv(plan.local, src, dst, nc, rnd)
+        elif plan.self_unpack is not None:
+            apply_copy_conv(plan.self_unpack, recv_buf, dst, nc, wid)
+        for r in reqs:
+            r.wait()
+        for blk in plan.peers:
+            if blk.unpack is not None:
+                apply_copy_conv(blk.unpack, recv_buf, dst, nc, wid)
+
     # ------------------------------------------------------------------
     # GPU execution — native HIP engine only.
     # ------------------------------------------------------------------
@@ -214,11 +309,12 @@ class Transposition:
 
 
 def transpose_into(dest: PencilArray, src: PencilArray,
-                   method: str = "grouped") -> PencilArray:
+                   method: str = "grouped", wire_dtype=None) -> PencilArray:
     """``transpose!(dest, src; method)`` (Transpositions.jl:161-169)."""
     if dest is src:
         return dest
-    return Transposition(dest, src, method=method).execute()
+    return Transposition(dest, src, method=method,
+                         wire_dtype=wire_dtype).execute()
 
 
 class MultiTransposition:
@@ -236,10 +332,13 @@ class MultiTransposition:
     before any write of a destination.
 
     numpy arrays run the host mirror — one single-field Transposition per
-    field, which pins the semantics, not the performance."""
+    field, which pins the semantics, not the performance.
+
+    ``wire_dtype``: a reduced-precision wire for every field, as in
+    :class:`Transposition`."""
 
     def __init__(self, dests: Sequence[PencilArray],
-                 srcs: Sequence[PencilArray]):
+                 srcs: Sequence[PencilArray], wire_dtype=None):
         dests, srcs = list(dests), list(srcs)
         if len(dests) != len(srcs):
             raise ValueError(
@@ -287,6 +386,8 @@ class MultiTransposition:
                     f"{storage(s0)}")
         self.srcs = srcs
         self.dests = dests
+        self.wire_dtype = wire_dtype
+        self.wire = _wire_pair(d0, s0, wire_dtype)
         self.aliased = any(_arrays_alias(s.data, d.data)
                            for s in srcs for d in dests)
         self.plan: TransposePlan = build_plan(
@@ -304,7 +405,7 @@ class MultiTransposition:
         else:
             srcs = self.srcs
         for d, s in zip(self.dests, srcs):
-            Transposition(d, s).execute()
+            Transposition(d, s, wire_dtype=self.wire_dtype).execute()
 
     def execute(self, sync: bool = True):
         """Run the transposes; ``sync=False`` returns with the work enqueued
@@ -333,9 +434,9 @@ class MultiTransposition:
 
 
 def transpose_many_into(dests: Sequence[PencilArray],
-                        srcs: Sequence[PencilArray]):
+                        srcs: Sequence[PencilArray], wire_dtype=None):
     """``transpose!`` of every pair ``dests[i] <- srcs[i]`` in one call."""
-    return MultiTransposition(dests, srcs).execute()
+    return MultiTransposition(dests, srcs, wire_dtype=wire_dtype).execute()
 
 
 # ----------------------------------------------------------------------
@@ -346,9 +447,14 @@ def transpose_many_into(dests: Sequence[PencilArray],
 
 def run_transpose_sim(dests: Sequence[PencilArray],
                       srcs: Sequence[PencilArray],
-                      staging_out=None) -> None:
+                      staging_out=None, wire_dtype=None) -> None:
     """``staging_out``, if a dict, receives the final ``send``/``recv``
-    staging buffers per rank."""
+    staging buffers per rank.  ``wire_dtype``: a reduced-precision wire (see
+    :class:`Transposition`); the staging buffers then hold wire scalars."""
+    if wire_dtype is not None:
+        return run_transpose_sim_many([[d] for d in dests],
+                                      [[s] for s in srcs], staging_out,
+                                      wire_dtype=wire_dtype)
     nranks = len(srcs)
     plans = [build_plan(s.pencil, d.pencil, r, s.extra_dims,
                         aliased=_arrays_alias(s.data, d.data))
@@ -406,14 +512,20 @@ def run_transpose_sim(dests: Sequence[PencilArray],
 
 def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
-                           staging_out=None) -> None:
+                           staging_out=None, wire_dtype=None) -> None:
     """:func:`run_transpose_sim` for ``n`` fields per rank with the
     multi-field staging layout (plan.py): every field of a rank is packed
     into ONE n-fold send buffer, and the exchange is ONE slice copy per peer
     pair of ``n * c`` elements — the "one message per peer" contract.
     ``dests_per_rank[r][f]`` / ``srcs_per_rank[r][f]`` is field ``f`` on
     rank ``r``.  ``staging_out``, if a dict, receives the final
-    ``send``/``recv`` buffers per rank (tests compare them)."""
+    ``send``/``recv`` buffers per rank (tests compare them).
+    ``wire_dtype``: a reduced-precision wire; the staging buffers then hold
+    wire scalars (bfloat16 as uint16 patterns), packs narrow, unpacks widen
+    and the local copy rounds."""
+    if wire_dtype is not None:
+        return _run_sim_many_wire(dests_per_rank, srcs_per_rank, staging_out,
+                                  wire_dtype)
     nranks = len(srcs_per_rank)
     n = len(srcs_per_rank[0])
     if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
@@ -474,6 +586,76 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                 if blk.unpack is not None:
                     apply_copy(copydesc_many(p, n, f, 2, blk.peer_k),
                                recv_bufs[r], dflat[r][f])
+    if staging_out is not None:
+        staging_out["send"] = send_bufs
+        staging_out["recv"] = recv_bufs
+
+
+def _run_sim_many_wire(dests_per_rank, srcs_per_rank, staging_out,
+                       wire_dtype) -> None:
+    """run_transpose_sim_many with a reduced-precision wire: the same
+    staging layout in elements, every buffer in wire scalars."""
+    nranks = len(srcs_per_rank)
+    n = len(srcs_per_rank[0])
+    if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
+            any(len(x) != n for x in dests_per_rank):
+        raise ValueError("every rank needs the same number (>= 1) of fields")
+    s00 = next(s for row in srcs_per_rank for s in row)
+    pair = _wire_pair(dests_per_rank[0][0], s00, wire_dtype)
+    nc = s00.ncomp * pair.comps
+    nar, wid, rnd = _wire_convs(pair)
+    plans = []
+    for r in range(nranks):
+        s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
+        aliased = any(_arrays_alias(s.data, d.data)
+                      for s in srcs_per_rank[r] for d in dests_per_rank[r])
+        plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
+                                aliased=aliased))
+    sflat = [[s.data.view(pair.stored) for s in row] for row in srcs_per_rank]
+    dflat = [[d.data.view(pair.stored) for d in row]
+             for row in dests_per_rank]
+    send_bufs, recv_bufs = [], []
+    for p in plans:
+        ns, nr = buffer_nelem_many(p, n)
+        send_bufs.append(np.empty(ns * nc, dtype=pair.carrier))
+        recv_bufs.append(np.empty(nr * nc, dtype=pair.carrier))
+
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for blk in p.peers:
+                if blk.pack is not None:
+                    apply_copy_conv(copydesc_many(p, n, f, 1, blk.peer_k),
+                                    sflat[r][f], send_bufs[r], nc, nar)
+            if p.self_pack is not None:
+                apply_copy_conv(copydesc_many(p, n, f, 3), sflat[r][f],
+                                recv_bufs[r], nc, nar)
+    for r, p in enumerate(plans):
+        for f in range(n):
+            if p.local is not None:
+                apply_copy_conv(p.local, sflat[r][f], dflat[r][f], nc, rnd)
+            elif p.self_unpack is not None:
+                apply_copy_conv(copydesc_many(p, n, f, 4), recv_bufs[r],
+                                dflat[r][f], nc, wid)
+
+    for r, p in enumerate(plans):
+        if p.r_dim is None:
+            continue
+        for blk in p.peers:
+            if blk.peer_k == p.my_k or blk.send_nelem == 0:
+                continue
+            so, sn, _, _ = peer_message(p, n, blk.peer_k)
+            q = plans[blk.global_rank]
+            _, _, ro, rn = peer_message(q, n, p.my_k)
+            assert rn == sn, (r, blk.peer_k, sn, rn)
+            recv_bufs[blk.global_rank][ro * nc:(ro + rn) * nc] = \
+                send_bufs[r][so * nc:(so + sn) * nc]
+
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for blk in p.peers:
+                if blk.unpack is not None:
+                    apply_copy_conv(copydesc_many(p, n, f, 2, blk.peer_k),
+                                    recv_bufs[r], dflat[r][f], nc, wid)
     if staging_out is not None:
         staging_out["send"] = send_bufs
         staging_out["recv"] = recv_bufs
