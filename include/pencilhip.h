@@ -148,6 +148,49 @@ pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
                               pa_plan **out);
 /* The wire pair of a plan, or 0 for an ordinary plan. */
 int pa_plan_wire(const pa_plan *p);
+
+/* Truncated transpose: move only a kept product set of indices — the other
+ * standard lever of a pseudo-spectral code (after the 2/3 rule a third of the
+ * modes along every transformed dimension are known zeros; the reference has
+ * no such option, its transpose! moves every element of src).
+ * The keep set is K = K_0 x ... x K_{N-1} over the LOGICAL dims with
+ *     K_d = [0, keep_lo[d]) U [N_d - keep_hi[d], N_d),
+ * keep_lo, keep_hi >= 0 and keep_lo[d] + keep_hi[d] <= N_d: keep_hi = 0 for an
+ * r2c dim, low and high wavenumbers for a c2c dim, (N_d, 0) keeps everything.
+ * extra_dims and element components are never truncated.
+ * Contract, T being the transposition of the same pencil pair:
+ *     dest[i] = src[i] bit for bit      for global index i in K,
+ *     dest[i] = +0 (all zero bytes)     for i not in K with PA_FILL_ZERO,
+ *     dest[i] unchanged                 for i not in K with PA_FILL_NONE.
+ * Every block of the ordinary plan (a peer's send region, a peer's recv
+ * region, the self block) is intersected with K: up to 2^N sub-boxes, low
+ * range before high range, dim 0 varying fastest, empty ones dropped; the two
+ * ranges of a dim merge when keep_lo + keep_hi == N_d.  Each sub-box is a
+ * staging block of its own (offset o_s, count c_s; the sub-boxes of a peer
+ * are consecutive, peers in ascending order) with one ordinary descriptor:
+ * field f of n sits at n*o_s + f*c_s, and peer k's message is still ONE
+ * contiguous range of the KEPT bytes (pa_plan_peer_message); a peer with
+ * nothing kept has a zero-byte message and is left out of the exchange on
+ * both sides.  Sender and receiver derive the same sub-boxes.
+ * pa_plan_buffer_sizes[_many], pa_plan_peer_message, the three stage calls,
+ * pa_transpose_execute[_many], pa_transpose_wait, timing, PA_PLAN_ALIASED and
+ * pa_plan_stage_launches work with the kept sizes; pa_transpose_execute runs
+ * the n = 1 stage path and its hipMalloc fallback is sized in kept bytes.
+ * With PA_FILL_ZERO the local stage also zero-fills the windows of the
+ * destination outside K (pa_plan_filldesc) with ONE grouped launch
+ * (PA_KERNEL_FILL); fill and copy windows are disjoint, so no ordering
+ * between them is needed.  PENCILHIP_EXCHANGE_CHUNKS does not apply.  There
+ * is no keep plan with a wire pair yet.  With the full keep set the tables,
+ * sizes and launches equal those of pa_plan_create_comp. */
+#define PA_FILL_NONE 0
+#define PA_FILL_ZERO 1
+pa_status pa_plan_create_keep(const pa_pencil *pin, const pa_pencil *pout,
+                              int64_t scalar_size, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              const int64_t *keep_lo, const int64_t *keep_hi,
+                              int fill, pa_plan **out);
+/* 1 for a keep plan (lo[N], hi[N], *fill written where non-NULL), else 0. */
+int pa_plan_keep(const pa_plan *p, int64_t *lo, int64_t *hi, int *fill);
 void pa_plan_destroy(pa_plan *p);
 
 /* Subgroup communicator for the exchange (required when the subgroup size
@@ -278,13 +321,33 @@ pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
  * Staging is taken from pa_plan_set_buffers, else assumed 256-byte aligned.
  * At most max_rows rows are written; *nrows is the full count.  The stage
  * calls execute exactly this list.  A wire plan reports its converting
- * kernels (PA_KERNEL_CVT_*) as ungrouped rows, one per descriptor. */
+ * kernels (PA_KERNEL_CVT_*) as ungrouped rows, one per descriptor.  A keep
+ * plan has one entry per sub-box and field, and its local stage ends with
+ * ONE grouped PA_KERNEL_FILL row holding the fill entries of every field. */
 #define PA_STAGE_PACK   0
 #define PA_STAGE_LOCAL  1
 #define PA_STAGE_UNPACK 2
 pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
                                  const void *const *srcs, void *const *dsts,
                                  int max_rows, int64_t (*rows)[4], int *nrows);
+
+/* Keep plans (pa_plan_create_keep): pa_plan_copydesc[_many] fail on them and
+ * name pa_plan_copydesc_sub.  pa_plan_nsub: the non-empty sub-boxes behind
+ * `which` (0..4 as in pa_plan_copydesc; peer k for 1 and 2); 0 on any other
+ * plan.  pa_plan_copydesc_sub: sub-box s of field f of n, in the form of
+ * pa_plan_copydesc_many.  pa_plan_nfill / pa_plan_filldesc: the zero-filled
+ * windows of the output parent, destination-only descriptors in element
+ * units (unit axes dropped, contiguous axes merged): for d = 0..N-1, (kept in
+ * dims < d) x (dropped range of dim d) x (everything in dims > d), clipped to
+ * this rank, empty ones dropped; none with PA_FILL_NONE. */
+int pa_plan_nsub(const pa_plan *p, int which, int k);
+pa_status pa_plan_copydesc_sub(const pa_plan *p, int n, int f, int which,
+                               int k, int s, int64_t *nd, int64_t *dims,
+                               int64_t *sstr, int64_t *soff, int64_t *dstr,
+                               int64_t *doff);
+int pa_plan_nfill(const pa_plan *p);
+pa_status pa_plan_filldesc(const pa_plan *p, int i, int64_t *nd,
+                           int64_t *dims, int64_t *dstr, int64_t *doff);
 
 /* Stage tables this plan holds in its cache (at most 12, least recently used
  * evicted): one per (n, stage, array set) that has run.  A repeated call on
@@ -399,6 +462,28 @@ pa_status pa_copy_kernel_kind_wire(int nd, const int64_t *dims,
                                    int wire, int op, int64_t ncomp,
                                    const void *src, const void *dst,
                                    int64_t out[5]);
+
+/* ---- zero fill (truncated transposes) ---------------------------------- */
+/* Zero one destination-only window on the device (the kernel body a keep
+ * plan's grouped fill runs): dst[doff + sum j_i*dstr_i] = 0 for j over dims,
+ * in elements of scalar_size * ncomp bytes.  An empty window launches
+ * nothing.  dst must be aligned to its scalar. */
+pa_status pa_device_fill_zero(int nd, const int64_t *dims,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp, void *dst,
+                              void *stream);
+/* Which stores the fill makes (host-only; dst is used for its alignment
+ * only).  out = {kind, store_bytes}: PA_KERNEL_FILL, or PA_KERNEL_NONE with
+ * 0 for an empty window.  store_bytes is the widest of 16, 8, 4 that divides
+ * the base pointer, the offset and every non-unit stride in bytes, and the
+ * run length in bytes (a window contiguous along its fastest axis, one lane
+ * per store) or the element size (any other window, one lane per element);
+ * else 1. */
+#define PA_KERNEL_FILL 12
+pa_status pa_fill_kernel_kind(int nd, const int64_t *dims,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp,
+                              const void *dst, int64_t out[2]);
 
 #ifdef __cplusplus
 }

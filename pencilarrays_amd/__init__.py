@@ -21,7 +21,8 @@ from .permutations import (
 from .topology import Topology, dims_create
 from .pencil import Pencil
 from .array import PencilArray
-from .plan import CopyDesc, TransposePlan, build_plan, normalize_desc
+from .plan import (CopyDesc, FillDesc, TransposePlan, build_plan, fourier_keep,
+                   normalize_desc)
 from .transpositions import (
     MultiTransposition,
     Transposition,
@@ -47,6 +48,7 @@ __all__ = [
     "MPIIOFile", "reductions", "round_wire",
     "gather", "gather_sim", "gather_dist",
     "CopyDesc", "TransposePlan", "build_plan", "normalize_desc",
+    "FillDesc", "fourier_keep",
     "identity_perm", "perm_apply", "perm_unapply", "perm_inv",
     "perm_relative", "perm_append",
 ]

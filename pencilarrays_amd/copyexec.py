@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .plan import CopyDesc
+from .plan import CopyDesc, FillDesc
 
 
 def apply_copy(desc: CopyDesc, src_flat: np.ndarray, dst_flat: np.ndarray) -> None:
@@ -54,3 +54,18 @@ def apply_copy_conv(desc: CopyDesc, src_scalars: np.ndarray,
         strides=tuple(s * ncomp * di for s in desc.dstrides) + (di,),
     )
     dv[...] = conv(sv)
+
+
+def apply_fill(desc: FillDesc, dst_flat: np.ndarray) -> None:
+    """dst[doffset + Σ j·dstrides] = +0 (all zero bytes): the fill of a
+    truncated transpose outside its keep set."""
+    if desc.nelem == 0:
+        return
+    assert dst_flat.ndim == 1
+    isz = dst_flat.itemsize
+    dv = np.lib.stride_tricks.as_strided(
+        dst_flat[desc.doffset:],
+        shape=desc.dims,
+        strides=tuple(s * isz for s in desc.dstrides),
+    )
+    dv[...] = np.zeros((), dtype=dst_flat.dtype)

@@ -637,6 +637,78 @@ __global__ __launch_bounds__(64 * NROWS) void k_group_tile_vs(
                                       bid - first[e]);
 }
 
+/* ---- grouped zero fill: the destination outside a keep set -------------
+ *
+ * A truncated transpose (pa_plan_create_keep) writes only the kept indices;
+ * the rest of the destination must read +0 for the next FFT.  Each entry is a
+ * destination-only window, already scaled by the host to `width`-byte words
+ * (select_fill): on a window contiguous along axis 0 a lane stores one word
+ * of the run (m = 1, dims[0] = words in the run); on any other window a lane
+ * owns one element and stores its m words.  Entry lookup is that of the other
+ * grouped kernels, so nd, width, m and every dim and stride sit on scalar
+ * registers.  No LDS, no scratch. */
+struct GFill {
+    int nd;
+    int width; /* bytes per store: 16, 8, 4 or 1 */
+    int m;     /* stores per lane */
+    int pad_;
+    int64_t dims[MAXND], dstr[MAXND]; /* lanes per axis; strides in words */
+    int64_t doff, total;              /* words; lanes */
+    void *dst;
+};
+
+template <typename T> __device__ __forceinline__ T zero_word()
+{
+    return (T)0;
+}
+template <> __device__ __forceinline__ uint4 zero_word<uint4>()
+{
+    return make_uint4(0u, 0u, 0u, 0u);
+}
+
+template <typename T>
+__device__ __forceinline__ void fill_body(const GFill &g, int64_t b)
+{
+    const int64_t idx = b * blockDim.x + threadIdx.x;
+    if (idx >= g.total) return;
+    int64_t o = idx, off = g.doff;
+    for (int a = 0; a < g.nd; a++) {
+        const int64_t j = o % g.dims[a];
+        o /= g.dims[a];
+        off += j * g.dstr[a];
+    }
+    T *q = (T *)g.dst + off;
+    for (int w = 0; w < g.m; w++) q[w] = zero_word<T>();
+}
+
+__device__ __forceinline__ void fill_entry(const GFill &g, int64_t b)
+{
+    if (g.width == 16)
+        fill_body<uint4>(g, b);
+    else if (g.width == 8)
+        fill_body<uint64_t>(g, b);
+    else if (g.width == 4)
+        fill_body<uint32_t>(g, b);
+    else
+        fill_body<uint8_t>(g, b);
+}
+
+__global__ __launch_bounds__(256) void k_group_fill(
+    const int64_t *__restrict__ first, const GFill *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    fill_entry(ent[e], bid - first[e]);
+}
+
+/* one entry passed by value: pa_device_fill_zero (same body) */
+__global__ __launch_bounds__(256) void k_fill(GFill g)
+{
+    fill_entry(g, (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
 /* ---- converting kernels: reduced-precision wire ------------------------
  *
  * A wire pair (stored scalar -> wire scalar: f64->f32, f32->f16, f32->bf16)
@@ -1745,6 +1817,94 @@ static pa_status launch_desc_cvt(const CopyDescH &dn, int wire, int op,
     return launch_cvt_sel(k, src, dst, stream);
 }
 
+/* ---- zero fill: descriptor, store width, launch ----------------------- */
+
+struct FillDescH {
+    int nd = 0;
+    int64_t dims[MAXND] = {0}, dstr[MAXND] = {0};
+    int64_t doff = 0, total = 0;
+};
+
+/* drop unit axes, sort by ascending stride, merge contiguous axes */
+static FillDescH normalize_fill(int nd, const int64_t *dims,
+                                const int64_t *dstr, int64_t doff)
+{
+    struct Axis { int64_t dim, ds; };
+    std::vector<Axis> ax;
+    for (int i = 0; i < nd; i++)
+        if (dims[i] != 1) ax.push_back({dims[i], dstr[i]});
+    if (ax.empty()) ax.push_back({1, 1});
+    std::stable_sort(ax.begin(), ax.end(),
+                     [](const Axis &a, const Axis &b) { return a.ds < b.ds; });
+    std::vector<Axis> m{ax[0]};
+    for (size_t i = 1; i < ax.size(); i++) {
+        Axis &p = m.back();
+        if (ax[i].ds == p.ds * p.dim)
+            p.dim *= ax[i].dim;
+        else
+            m.push_back(ax[i]);
+    }
+    FillDescH out;
+    out.nd = (int)m.size();
+    out.total = 1;
+    for (int i = 0; i < out.nd; i++) {
+        out.dims[i] = m[i].dim;
+        out.dstr[i] = m[i].ds;
+        out.total *= m[i].dim;
+    }
+    out.doff = doff;
+    return out;
+}
+
+/* The fill decision, made in ONE place like select_kernel(): the widest
+ * store of 16, 8 or 4 bytes that divides the base pointer, the offset and
+ * every non-unit stride in bytes, and the run length (a contiguous window)
+ * or the element (any other window); else single bytes. */
+struct FillSel {
+    int kind = PA_KERNEL_NONE;
+    GFill g;
+    int64_t nblocks = 0;
+};
+
+static pa_status select_fill(const FillDescH &d, int64_t esz, const void *dst,
+                             FillSel *out)
+{
+    *out = FillSel();
+    memset(&out->g, 0, sizeof out->g);
+    if (esz <= 0) return fail("bad element size");
+    if (d.total == 0) return 0;
+    const bool run = d.dstr[0] == 1;
+    const int64_t unit = run ? d.dims[0] * esz : esz; /* bytes a word divides */
+    int64_t W = 1;
+    for (int64_t cand : {16, 8, 4}) {
+        bool ok = ((uintptr_t)dst & (uintptr_t)(cand - 1)) == 0 &&
+                  unit % cand == 0 && (d.doff * esz) % cand == 0;
+        for (int a = run ? 1 : 0; a < d.nd && ok; a++)
+            if ((d.dstr[a] * esz) % cand) ok = false;
+        if (ok) { W = cand; break; }
+    }
+    GFill &g = out->g;
+    g.nd = d.nd;
+    g.width = (int)W;
+    g.m = run ? 1 : (int)(esz / W);
+    g.total = 1;
+    for (int a = 0; a < MAXND; a++) {
+        g.dims[a] = a < d.nd ? d.dims[a] : 1;
+        g.dstr[a] = a < d.nd ? d.dstr[a] * esz / W : 0;
+        g.total *= g.dims[a];
+    }
+    if (run) {
+        g.total = g.total / g.dims[0] * (unit / W);
+        g.dims[0] = unit / W;
+        g.dstr[0] = 1;
+    }
+    g.doff = d.doff * esz / W;
+    g.dst = (void *)dst;
+    out->kind = PA_KERNEL_FILL;
+    out->nblocks = grid_exact(g.total, 256);
+    return 0;
+}
+
 /* ================= metadata ======================================== */
 
 struct Range { int64_t lo, hi; };
@@ -1828,6 +1988,13 @@ struct pa_comm {
 
 /* ================= plan ============================================ */
 
+/* one sub-box of a block on a keep plan: its staging block (offset and
+ * count in elements) and its descriptor */
+struct SubC {
+    int64_t off, n;
+    CopyDescH d;
+};
+
 struct PeerBlockC {
     int k, grank;
     int64_t send_off, recv_off, send_n, recv_n;
@@ -1840,6 +2007,8 @@ struct PeerBlockC {
     int64_t recv_outer = 1, recv_rowelems = 0;
     CopyDescH unpack_raw; /* un-normalized: nd = n+E, axis nd-1 = outer */
     bool has_unpack_raw = false;
+    /* keep plans: one staging block per non-empty sub-box of the block */
+    std::vector<SubC> pack_subs, unpack_subs;
 };
 
 struct StageTable; /* multi-field stage: launch list + device tables */
@@ -1897,6 +2066,17 @@ struct pa_plan {
      * keyed on (n, stage, every pointer the stage touches) */
     std::vector<StageTable *> tables;
     uint64_t table_clock = 0;
+    /* truncated transpose (pa_plan_create_keep): K_d = [0, keep_lo[d]) U
+     * [N_d - keep_hi[d], N_d) per logical dim.  Every count and offset above
+     * is then in KEPT elements, the single descriptors are unset and the
+     * sub-box tables below take their place; fills lists the destination
+     * windows outside the keep set (PA_FILL_ZERO). */
+    bool keep = false;
+    int fill = PA_FILL_NONE;
+    std::vector<int64_t> keep_lo, keep_hi;
+    std::vector<CopyDescH> local_subs;
+    std::vector<SubC> self_pack_subs, self_unpack_subs;
+    std::vector<FillDescH> fills;
 };
 
 static void free_stage_tables(pa_plan *p);
@@ -2070,6 +2250,153 @@ static CopyDescH chunk_of_raw(const CopyDescH &raw, int64_t lo, int64_t hi)
 static inline int64_t chunk_lo(int64_t outer, int c, int C)
 {
     return outer * c / C;
+}
+
+/* ---- truncated transposes: sub-boxes of a block under a keep set ------ */
+
+struct Box { Range r[MAXND]; };
+
+/* the ranges of K_d, low before high; adjacent ranges merge */
+static std::vector<Range> keep_ranges(int64_t a, int64_t b, int64_t N)
+{
+    if (a + b >= N) return {Range{0, N}};
+    return {Range{0, a}, Range{N - b, N}};
+}
+
+/* every combination of one range per dim clipped to `clip`, dim 0 varying
+ * fastest, empty boxes dropped */
+static void box_product(int n, const std::vector<Range> *per_dim,
+                        const Range *clip, std::vector<Box> *out)
+{
+    int idx[MAXND] = {0};
+    while (true) {
+        Box b;
+        bool empty = false;
+        for (int d = 0; d < n; d++) {
+            range_intersect(per_dim[d][idx[d]], clip[d], &b.r[d]);
+            if (b.r[d].hi <= b.r[d].lo) empty = true;
+        }
+        if (!empty) out->push_back(b);
+        int d = 0;
+        for (; d < n; d++) {
+            if (++idx[d] < (int)per_dim[d].size()) break;
+            idx[d] = 0;
+        }
+        if (d == n) return;
+    }
+}
+
+static void sub_boxes(const pa_plan &pl, const Range *region,
+                      std::vector<Box> *out)
+{
+    std::vector<Range> per_dim[MAXND];
+    for (int d = 0; d < pl.Pi.n; d++)
+        per_dim[d] = keep_ranges(pl.keep_lo[d], pl.keep_hi[d],
+                                 pl.Pi.size_global[d]);
+    box_product(pl.Pi.n, per_dim, region, out);
+}
+
+static int64_t box_nelem(const pa_plan &pl, const Box &b)
+{
+    return region_nelem(pl.Pi.n, b.r) * prod_extra(pl);
+}
+
+/* pack of a box: src window -> column-major staging block at `off` */
+static SubC pack_sub(const pa_plan &pl, const Box &b, int64_t off)
+{
+    int64_t dims[2 * MAXND], str[2 * MAXND], woff;
+    int kk;
+    window_desc(pl.Pi, pl.rank, pl.extra, b.r, dims, str, &woff, &kk);
+    int64_t cstr[2 * MAXND], acc = 1;
+    for (int i = 0; i < kk; i++) {
+        cstr[i] = acc;
+        acc *= dims[i];
+    }
+    return SubC{off, box_nelem(pl, b),
+                normalize_desc(kk, dims, str, woff, cstr, off)};
+}
+
+/* unpack of a box: staging block at `off` (Pi memory order) -> dst window */
+static SubC unpack_sub(const pa_plan &pl, const Box &b, int64_t off)
+{
+    const int n = pl.Pi.n, e = pl.E;
+    int64_t bdims[2 * MAXND], bstr[2 * MAXND], acc = 1;
+    for (int i = 0; i < n; i++)
+        bdims[i] = b.r[pl.Pi.perm[i]].hi - b.r[pl.Pi.perm[i]].lo;
+    for (int e2 = 0; e2 < e; e2++) bdims[n + e2] = pl.extra[e2];
+    for (int i = 0; i < n + e; i++) {
+        bstr[i] = acc;
+        acc *= bdims[i];
+    }
+    return SubC{off, box_nelem(pl, b), unpack_desc(pl, b.r, bdims, bstr, off)};
+}
+
+/* fused local copy of a box: src window -> dst window */
+static CopyDescH local_sub(const pa_plan &pl, const Box &b)
+{
+    int64_t dims[2 * MAXND], str[2 * MAXND], off;
+    int kk;
+    window_desc(pl.Pi, pl.rank, pl.extra, b.r, dims, str, &off, &kk);
+    return unpack_desc(pl, b.r, dims, str, off);
+}
+
+/* the self block under the keep set: fused copies, or in aliased mode staged
+ * through the recv buffer from element offset `off`; returns the end offset */
+static int64_t keep_self_block(pa_plan *pl, const Range *region, int64_t off)
+{
+    std::vector<Box> boxes;
+    sub_boxes(*pl, region, &boxes);
+    for (auto &b : boxes) {
+        if (pl->aliased) {
+            pl->self_pack_subs.push_back(pack_sub(*pl, b, off));
+            pl->self_unpack_subs.push_back(unpack_sub(*pl, b, off));
+            off += box_nelem(*pl, b);
+        } else
+            pl->local_subs.push_back(local_sub(*pl, b));
+    }
+    return off;
+}
+
+/* The complement of the keep set inside this rank's destination range: for
+ * d = 0..N-1, (kept in dims < d) x (dropped range of dim d) x (everything in
+ * dims > d), as windows of the output parent. */
+static void keep_fills(pa_plan *pl)
+{
+    const pa_pencil &Po = pl->Po;
+    const int n = Po.n;
+    if (prod_extra(*pl) == 0) return;
+    Range axo[MAXND];
+    axes_for_rank(Po, pl->rank, axo);
+    int64_t mem_o[2 * MAXND], pst_o[2 * MAXND];
+    int k;
+    parent_strides(Po, pl->rank, pl->extra, mem_o, pst_o, &k);
+    for (int d = 0; d < n; d++) {
+        const int64_t a = pl->keep_lo[d], N = Po.size_global[d];
+        const int64_t hi = N - pl->keep_hi[d];
+        if (hi <= a) continue;
+        std::vector<Range> per_dim[MAXND];
+        for (int j = 0; j < n; j++) {
+            if (j < d)
+                per_dim[j] = keep_ranges(pl->keep_lo[j], pl->keep_hi[j],
+                                         Po.size_global[j]);
+            else if (j == d)
+                per_dim[j] = {Range{a, hi}};
+            else
+                per_dim[j] = {Range{0, Po.size_global[j]}};
+        }
+        std::vector<Box> boxes;
+        box_product(n, per_dim, axo, &boxes);
+        for (auto &b : boxes) {
+            int64_t dims[2 * MAXND], off = 0;
+            for (int i = 0; i < n; i++) {
+                const int ld = Po.perm[i];
+                dims[i] = b.r[ld].hi - b.r[ld].lo;
+                off += (b.r[ld].lo - axo[ld].lo) * pst_o[i];
+            }
+            for (int e = 0; e < pl->E; e++) dims[n + e] = pl->extra[e];
+            pl->fills.push_back(normalize_fill(n + pl->E, dims, pst_o, off));
+        }
+    }
 }
 
 extern "C" {
@@ -2464,6 +2791,106 @@ pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
 
 int pa_plan_wire(const pa_plan *p) { return p ? p->wire : 0; }
 
+pa_status pa_plan_create_keep(const pa_pencil *pin, const pa_pencil *pout,
+                              int64_t scalar_size, int64_t ncomp, int e,
+                              const int64_t *extra_dims, int rank, int flags,
+                              const int64_t *keep_lo, const int64_t *keep_hi,
+                              int fill, pa_plan **out)
+{
+    if (!out || !pin || !pout) return fail("null argument");
+    if (!keep_lo || !keep_hi) return fail("null keep_lo / keep_hi");
+    if (fill != PA_FILL_NONE && fill != PA_FILL_ZERO)
+        return fail("fill must be PA_FILL_NONE (0) or PA_FILL_ZERO (1), got %d",
+                    fill);
+    for (int d = 0; d < pin->n; d++)
+        if (keep_lo[d] < 0 || keep_hi[d] < 0 ||
+            keep_lo[d] + keep_hi[d] > pin->size_global[d])
+            return fail("keep set of dim %d: (%lld, %lld) must satisfy a, b "
+                        ">= 0 and a + b <= %lld", d, (long long)keep_lo[d],
+                        (long long)keep_hi[d],
+                        (long long)pin->size_global[d]);
+    /* peers, their order and every validation are those of the ordinary
+     * plan; its block tables are then replaced by the sub-box tables */
+    pa_plan *pl = nullptr;
+    if (pa_status st = pa_plan_create_comp(pin, pout, scalar_size, ncomp, e,
+                                           extra_dims, rank, flags, &pl))
+        return st;
+    const int n = pin->n;
+    pl->keep = true;
+    pl->fill = fill;
+    pl->keep_lo.assign(keep_lo, keep_lo + n);
+    pl->keep_hi.assign(keep_hi, keep_hi + n);
+    pl->chunks = 1; /* the exchange of a keep plan is always a single group */
+    pl->has_local = pl->has_self = false;
+    pl->send_total = pl->recv_total = 0;
+    if (fill == PA_FILL_ZERO) keep_fills(pl);
+
+    if (pl->R < 0) {
+        Range region[MAXND];
+        axes_for_rank(*pin, rank, region);
+        pl->recv_total = keep_self_block(pl, region, 0);
+        *out = pl;
+        return 0;
+    }
+
+    int64_t coords[MAXND];
+    cart_coords(pin->topo, rank, coords);
+    Range axl_i[MAXND], axl_o[MAXND], self_region[MAXND];
+    axes_for_rank(*pin, rank, axl_i);
+    axes_for_rank(*pout, rank, axl_o);
+    int64_t isend = 0, irecv = 0;
+    for (auto &blk : pl->peers) {
+        int64_t pc[MAXND];
+        memcpy(pc, coords, sizeof(int64_t) * pin->topo.m);
+        pc[pl->R] = blk.k;
+        Range axp_o[MAXND], axp_i[MAXND], sr[MAXND], rr[MAXND];
+        axes_for_coords(*pout, pc, axp_o);
+        axes_for_coords(*pin, pc, axp_i);
+        for (int d = 0; d < n; d++) {
+            range_intersect(axl_i[d], axp_o[d], &sr[d]);
+            range_intersect(axl_o[d], axp_i[d], &rr[d]);
+        }
+        std::vector<Box> sb, rb;
+        sub_boxes(*pl, sr, &sb);
+        sub_boxes(*pl, rr, &rb);
+        blk.has_pack = blk.has_unpack = blk.has_unpack_raw = false;
+        blk.send_n = blk.recv_n = 0;
+        for (auto &b : sb) blk.send_n += box_nelem(*pl, b);
+        for (auto &b : rb) blk.recv_n += box_nelem(*pl, b);
+        blk.send_off = blk.recv_off = 0;
+        if (blk.k == pl->myk) {
+            memcpy(self_region, sr, sizeof(Range) * n);
+            continue;
+        }
+        blk.send_off = isend;
+        blk.recv_off = irecv;
+        for (auto &b : sb) {
+            blk.pack_subs.push_back(pack_sub(*pl, b, isend));
+            isend += blk.pack_subs.back().n;
+        }
+        for (auto &b : rb) {
+            blk.unpack_subs.push_back(unpack_sub(*pl, b, irecv));
+            irecv += blk.unpack_subs.back().n;
+        }
+    }
+    pl->send_total = isend;
+    if (pl->aliased) pl->peers[pl->myk].recv_off = irecv;
+    pl->recv_total = keep_self_block(pl, self_region, irecv);
+    *out = pl;
+    return 0;
+}
+
+int pa_plan_keep(const pa_plan *p, int64_t *lo, int64_t *hi, int *fill)
+{
+    if (!p || !p->keep) return 0;
+    for (size_t d = 0; d < p->keep_lo.size(); d++) {
+        if (lo) lo[d] = p->keep_lo[d];
+        if (hi) hi[d] = p->keep_hi[d];
+    }
+    if (fill) *fill = p->fill;
+    return 1;
+}
+
 void pa_plan_destroy(pa_plan *p)
 {
     if (!p) return;
@@ -2527,6 +2954,14 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
         if (p->recv_total)
             HIP_CHECK(hipMalloc(&p->recv_buf, p->recv_total * p->msg_esz));
         p->own_bufs = true;
+    }
+
+    /* a keep plan runs the n = 1 stage path: pack -> exchange -> local +
+     * fill -> unpack (the fallback above is sized in kept elements) */
+    if (p->keep) {
+        const void *srcs[1] = {src_parent};
+        void *dsts[1] = {dst_parent};
+        return pa_transpose_execute_many(p, 1, srcs, dsts, stream_);
     }
 
     if (p->timing) {
@@ -2739,8 +3174,8 @@ pa_status pa_plan_block_info(const pa_plan *p, int k, int64_t out[8])
     out[3] = b.recv_off;
     out[4] = b.send_n;
     out[5] = b.recv_n;
-    out[6] = b.has_pack;
-    out[7] = b.has_unpack;
+    out[6] = b.has_pack || !b.pack_subs.empty();
+    out[7] = b.has_unpack || !b.unpack_subs.empty();
     return 0;
 }
 
@@ -2749,6 +3184,9 @@ pa_status pa_plan_copydesc(const pa_plan *p, int which, int k, int64_t *nd,
                            int64_t *dstr, int64_t *doff)
 {
     const CopyDescH *d = nullptr;
+    if (p->keep)
+        return fail("a keep plan has one descriptor per sub-box: use "
+                    "pa_plan_copydesc_sub");
     if (which == 0) {
         if (!p->has_local) return fail("no local copy in plan");
         d = &p->local;
@@ -2959,10 +3397,54 @@ static pa_status many_desc(const pa_plan *p, int n, int f, int which, int k,
     return fail("bad which %d", which);
 }
 
+/* keep plans: how many sub-boxes `which` (of peer k) has, and sub-box s of
+ * field f with the multi-field rule applied to ITS staging block */
+static const std::vector<SubC> *sub_list(const pa_plan *p, int which, int k)
+{
+    if (which == 3) return &p->self_pack_subs;
+    if (which == 4) return &p->self_unpack_subs;
+    if (p->R < 0 || k < 0 || k >= (int)p->peers.size()) return nullptr;
+    if (which == 1) return &p->peers[k].pack_subs;
+    if (which == 2) return &p->peers[k].unpack_subs;
+    return nullptr;
+}
+
+static int sub_count(const pa_plan *p, int which, int k)
+{
+    if (which == 0) return (int)p->local_subs.size();
+    const std::vector<SubC> *l = sub_list(p, which, k);
+    return l ? (int)l->size() : 0;
+}
+
+static pa_status sub_desc(const pa_plan *p, int n, int f, int which, int k,
+                          int s, CopyDescH *out)
+{
+    if (!p->keep) return fail("not a keep plan");
+    if (n < 1) return fail("n must be >= 1");
+    if (f < 0 || f >= n) return fail("field %d out of range", f);
+    if (which < 0 || which > 4) return fail("bad which %d", which);
+    if (s < 0 || s >= sub_count(p, which, k))
+        return fail("no sub-box %d (which %d, peer %d)", s, which, k);
+    if (which == 0) {
+        *out = p->local_subs[s];
+        return 0;
+    }
+    const SubC &sb = (*sub_list(p, which, k))[s];
+    *out = sb.d;
+    const int64_t sh = many_shift(n, f, sb.off, sb.n);
+    if (which == 1 || which == 3)
+        out->doff += sh;
+    else
+        out->soff += sh;
+    return 0;
+}
+
 struct StageItem {
     KernelSel k;
     bool cvt = false; /* wire plan: the converting selection c runs, not k */
     CvtSel c;
+    bool fill = false; /* keep plan: a zero-fill entry, fs instead of k */
+    FillSel fs;
     const void *src;
     void *dst;
     int64_t nti = 0, njc = 0, nblocks = 0;
@@ -3052,10 +3534,8 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
                              const void *send_buf, void *recv_buf,
                              StageTable *t)
 {
-    auto add = [&](int f, int which, int k, const void *src,
-                   void *dst) -> pa_status {
-        CopyDescH d;
-        if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
+    auto add_desc = [&](const CopyDescH &d, int which, const void *src,
+                        void *dst) -> pa_status {
         StageItem it;
         it.src = src;
         it.dst = dst;
@@ -3105,6 +3585,79 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         t->launches.push_back(l);
         return 0;
     };
+    auto add = [&](int f, int which, int k, const void *src,
+                   void *dst) -> pa_status {
+        CopyDescH d;
+        if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
+        return add_desc(d, which, src, dst);
+    };
+    /* keep plans: every sub-box of `which` (of peer k) for field f */
+    auto add_subs = [&](int f, int which, int k, const void *src,
+                        void *dst) -> pa_status {
+        const int ns = sub_count(p, which, k);
+        for (int s = 0; s < ns; s++) {
+            CopyDescH d;
+            if (pa_status st = sub_desc(p, n, f, which, k, s, &d)) return st;
+            if (pa_status st = add_desc(d, which, src, dst)) return st;
+        }
+        return 0;
+    };
+    /* one zero-fill entry; all of a stage share ONE grouped launch */
+    auto add_fill = [&](const FillDescH &d, void *dst) -> pa_status {
+        StageItem it;
+        it.src = nullptr;
+        it.dst = dst;
+        it.fill = true;
+        if (pa_status st = select_fill(d, p->esz, dst, &it.fs)) return st;
+        it.nblocks = it.fs.nblocks;
+        if (it.nblocks == 0) return 0;
+        const int idx = (int)t->items.size();
+        t->items.push_back(it);
+        for (auto &l : t->launches)
+            if (l.grouped && l.kind == PA_KERNEL_FILL) {
+                l.items.push_back(idx);
+                l.nblocks += it.nblocks;
+                return 0;
+            }
+        StageLaunch l;
+        l.kind = PA_KERNEL_FILL;
+        l.word = 0;
+        l.grouped = true;
+        l.items.push_back(idx);
+        l.nblocks = it.nblocks;
+        t->launches.push_back(l);
+        return 0;
+    };
+
+    if (p->keep) {
+        for (int f = 0; f < n; f++) {
+            const void *src = srcs ? srcs[f] : nullptr;
+            void *dst = dsts ? dsts[f] : nullptr;
+            if (stage == STAGE_PACK) {
+                for (auto &b : p->peers)
+                    if (pa_status st = add_subs(f, 1, b.k, src,
+                                                (void *)send_buf))
+                        return st;
+                if (pa_status st = add_subs(f, 3, 0, src, recv_buf))
+                    return st;
+            } else if (stage == STAGE_LOCAL) {
+                if (pa_status st = add_subs(f, 0, 0, src, dst)) return st;
+                if (pa_status st = add_subs(f, 4, 0, recv_buf, dst))
+                    return st;
+            } else {
+                for (auto &b : p->peers)
+                    if (pa_status st = add_subs(f, 2, b.k, recv_buf, dst))
+                        return st;
+            }
+        }
+        /* the fill entries of every field, after the copies of the stage */
+        if (stage == STAGE_LOCAL)
+            for (int f = 0; f < n; f++)
+                for (auto &fd : p->fills)
+                    if (pa_status st = add_fill(fd, dsts ? dsts[f] : nullptr))
+                        return st;
+        return 0;
+    }
 
     for (int f = 0; f < n; f++) {
         const void *src = srcs ? srcs[f] : nullptr;
@@ -3152,6 +3705,23 @@ static pa_status upload_stage(StageTable *t)
     for (auto &l : t->launches) {
         if (!l.grouped) continue;
         const size_t ne = l.items.size();
+        if (l.kind == PA_KERNEL_FILL) {
+            std::vector<char> fhost(ne * sizeof(int64_t) +
+                                    ne * sizeof(GFill));
+            int64_t *ffirst = (int64_t *)fhost.data();
+            char *fent = fhost.data() + ne * sizeof(int64_t);
+            int64_t facc = 0;
+            for (size_t i = 0; i < ne; i++) {
+                const StageItem &it = t->items[l.items[i]];
+                ffirst[i] = facc;
+                facc += it.nblocks;
+                memcpy(fent + i * sizeof(GFill), &it.fs.g, sizeof(GFill));
+            }
+            HIP_CHECK(hipMalloc(&l.d_mem, fhost.size()));
+            HIP_CHECK(hipMemcpy(l.d_mem, fhost.data(), fhost.size(),
+                                hipMemcpyHostToDevice));
+            continue;
+        }
         std::vector<char> host(ne * sizeof(int64_t) + ne * sizeof(GEntry));
         int64_t *first = (int64_t *)host.data();
         GEntry *ent = (GEntry *)(host.data() + ne * sizeof(int64_t));
@@ -3185,6 +3755,15 @@ static pa_status launch_group(const StageLaunch &l, hipStream_t stream)
         (const GEntry *)((const char *)l.d_mem + ne * sizeof(int64_t));
     const int W = l.word;
     dim3 grid;
+    if (l.kind == PA_KERNEL_FILL) {
+        if (pa_status gst = grid2d(l.nblocks, 256, &grid)) return gst;
+        hipLaunchKernelGGL(k_group_fill, grid, dim3(256), 0, stream, first,
+                           (const GFill *)((const char *)l.d_mem +
+                                           ne * sizeof(int64_t)),
+                           ne, l.nblocks);
+        HIP_CHECK(hipGetLastError());
+        return 0;
+    }
 #define GROUP_GRID(threads)                                                  \
     do {                                                                     \
         if (pa_status gst = grid2d(l.nblocks, threads, &grid)) return gst;   \
@@ -3264,7 +3843,7 @@ static pa_status many_check(const pa_plan *p, int n, int stage,
         for (int f = 0; f < n; f++)
             if (!dsts[f]) return fail("null dst pointer for field %d", f);
     }
-    if (p->own_bufs)
+    if (p->own_bufs && !(p->keep && n == 1))
         return fail("multi-field stages need staging buffers of "
                     "pa_plan_buffer_sizes_many bytes from pa_plan_set_buffers");
     if ((p->send_total > 0 && !p->send_buf) ||
@@ -3351,6 +3930,9 @@ pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
                                 int64_t *doff)
 {
     if (!p) return fail("null plan");
+    if (p->keep)
+        return fail("a keep plan has one descriptor per sub-box: use "
+                    "pa_plan_copydesc_sub");
     CopyDescH d;
     if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
     *nd = d.nd;
@@ -3399,6 +3981,97 @@ pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
 int pa_plan_stage_table_count(const pa_plan *p)
 {
     return p ? (int)p->tables.size() : 0;
+}
+
+/* ---- truncated transposes: introspection and the stand-alone fill ---- */
+
+int pa_plan_nsub(const pa_plan *p, int which, int k)
+{
+    if (!p || !p->keep || which < 0 || which > 4) return 0;
+    return sub_count(p, which, k);
+}
+
+pa_status pa_plan_copydesc_sub(const pa_plan *p, int n, int f, int which,
+                               int k, int s, int64_t *nd, int64_t *dims,
+                               int64_t *sstr, int64_t *soff, int64_t *dstr,
+                               int64_t *doff)
+{
+    if (!p) return fail("null plan");
+    CopyDescH d;
+    if (pa_status st = sub_desc(p, n, f, which, k, s, &d)) return st;
+    *nd = d.nd;
+    for (int i = 0; i < d.nd; i++) {
+        dims[i] = d.dims[i];
+        sstr[i] = d.sstr[i];
+        dstr[i] = d.dstr[i];
+    }
+    *soff = d.soff;
+    *doff = d.doff;
+    return 0;
+}
+
+int pa_plan_nfill(const pa_plan *p)
+{
+    return p && p->keep ? (int)p->fills.size() : 0;
+}
+
+pa_status pa_plan_filldesc(const pa_plan *p, int i, int64_t *nd,
+                           int64_t *dims, int64_t *dstr, int64_t *doff)
+{
+    if (!p || !p->keep) return fail("not a keep plan");
+    if (i < 0 || i >= (int)p->fills.size()) return fail("no fill box %d", i);
+    const FillDescH &d = p->fills[i];
+    *nd = d.nd;
+    for (int a = 0; a < d.nd; a++) {
+        dims[a] = d.dims[a];
+        dstr[a] = d.dstr[a];
+    }
+    *doff = d.doff;
+    return 0;
+}
+
+static pa_status fill_args(int nd, const int64_t *dims, const int64_t *dstr,
+                           int64_t doff, int64_t scalar_size, int64_t ncomp,
+                           const void *dst, FillSel *out)
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (scalar_size <= 0 || ncomp <= 0) return fail("bad element size");
+    for (int a = 0; a < nd; a++)
+        if (dims[a] < 0 || dstr[a] < 0) return fail("bad fill window");
+    FillDescH d = normalize_fill(nd, dims, dstr, doff);
+    return select_fill(d, scalar_size * ncomp, dst, out);
+}
+
+pa_status pa_device_fill_zero(int nd, const int64_t *dims,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp, void *dst,
+                              void *stream)
+{
+    FillSel k;
+    if (pa_status st =
+            fill_args(nd, dims, dstr, doff, scalar_size, ncomp, dst, &k))
+        return st;
+    if (k.kind == PA_KERNEL_NONE) return 0; /* empty window: no launch */
+    dim3 grid;
+    if (pa_status st = grid2d(k.nblocks, 256, &grid)) return st;
+    hipLaunchKernelGGL(k_fill, grid, dim3(256), 0, (hipStream_t)stream, k.g);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+pa_status pa_fill_kernel_kind(int nd, const int64_t *dims,
+                              const int64_t *dstr, int64_t doff,
+                              int64_t scalar_size, int64_t ncomp,
+                              const void *dst, int64_t out[2])
+{
+    if (!out) return fail("null output");
+    FillSel k;
+    if (pa_status st =
+            fill_args(nd, dims, dstr, doff, scalar_size, ncomp, dst, &k))
+        return st;
+    out[0] = k.kind;
+    out[1] = k.kind == PA_KERNEL_NONE ? 0 : k.g.width;
+    return 0;
 }
 
 pa_status pa_transpose_pack_many(pa_plan *p, int n, const void *const *srcs,

@@ -67,6 +67,9 @@ KERNEL_TILE_WIDE = 8
 KERNEL_CVT_LINEAR = 9
 KERNEL_CVT_TILE = 10
 KERNEL_CVT_GENERIC = 11
+# grouped zero fill of a truncated transpose (pa_fill_kernel_kind)
+KERNEL_FILL = 12
+FILL_NONE, FILL_ZERO = 0, 1
 KERNEL_NAMES = {
     KERNEL_NONE: "NONE", KERNEL_COPY_1D: "COPY_1D",
     KERNEL_COPY_1D_NT: "COPY_1D_NT", KERNEL_LINEAR: "LINEAR",
@@ -74,6 +77,7 @@ KERNEL_NAMES = {
     KERNEL_TILE_PK: "TILE_PK", KERNEL_GENERIC: "GENERIC",
     KERNEL_TILE_WIDE: "TILE_WIDE", KERNEL_CVT_LINEAR: "CVT_LINEAR",
     KERNEL_CVT_TILE: "CVT_TILE", KERNEL_CVT_GENERIC: "CVT_GENERIC",
+    KERNEL_FILL: "FILL",
 }
 
 # wire pairs (stored -> wire) and ops of a converting copy
@@ -200,18 +204,62 @@ def device_copy_wire(desc, wire: int, op: int, ncomp: int, src_ptr: int,
         VP(src_ptr), VP(dst_ptr), VP(stream)), "pa_device_copy_wire")
 
 
+class FillKernelKind(NamedTuple):
+    """pa_fill_kernel_kind: ``store_bytes`` per store of the zero fill."""
+    kind: int
+    store_bytes: int
+
+
+def _fill_fields(desc):
+    if hasattr(desc, "dstrides"):
+        return desc.dims, desc.dstrides, desc.doffset
+    return desc
+
+
+def fill_kernel_kind(desc, esz: int, dst_ptr: int = 0,
+                     ncomp: int = 1) -> FillKernelKind:
+    """Which stores ``pa_device_fill_zero`` / a keep plan's fill makes for the
+    destination-only window ``desc`` (a ``plan.FillDesc`` or ``(dims, dstr,
+    doff)``) of ``ncomp`` scalars of ``esz`` bytes; host-only."""
+    lib = load()
+    dims, dstr, doff = _fill_fields(desc)
+    nd = len(dims)
+    out = (I64 * 2)()
+    _check(lib, lib.pa_fill_kernel_kind(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*dstr), I64(doff), I64(esz),
+        I64(ncomp), VP(dst_ptr), out), "pa_fill_kernel_kind")
+    return FillKernelKind(int(out[0]), int(out[1]))
+
+
+def device_fill_zero(desc, esz: int, dst_ptr: int, stream: int = 0,
+                     ncomp: int = 1) -> None:
+    """Zero one destination-only window on the device
+    (pa_device_fill_zero)."""
+    lib = load()
+    dims, dstr, doff = _fill_fields(desc)
+    nd = len(dims)
+    _check(lib, lib.pa_device_fill_zero(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*dstr), I64(doff), I64(esz),
+        I64(ncomp), VP(dst_ptr), VP(stream)), "pa_device_fill_zero")
+
+
 class NativePlan:
     """pa_plan plus the pa_topology/pa_pencil handles it needs.  Plan
     building is host-only (works without a GPU); execute needs one."""
 
     def __init__(self, Pi, Po, rank: int, elem_size: int,
                  extra_dims: Tuple[int, ...] = (), aliased: bool = False,
-                 ncomp: int = 1, wire: Optional[int] = None):
+                 ncomp: int = 1, wire: Optional[int] = None,
+                 keep=None, fill: int = FILL_ZERO):
         """``ncomp > 1``: elements of ``ncomp`` scalars of ``elem_size``
         bytes, components fastest (pa_plan_create_comp).  ``wire``: a wire
         pair code (WIRE_F64_F32, ...) for a reduced-precision wire plan
         (pa_plan_create_wire); ``elem_size`` is then the stored scalar
-        size."""
+        size.  ``keep``: ``(a, b)`` per logical dim for a truncated transpose
+        (pa_plan_create_keep) with ``fill`` FILL_ZERO or FILL_NONE."""
+        if keep is not None and wire is not None:
+            raise ValueError(
+                "a keep set together with a wire pair is not supported")
         lib = self.lib = load()
         topo = Pi.topology
         # both pa_pencils are built against ONE pa_topology handle, so the
@@ -241,7 +289,26 @@ class NativePlan:
         e = len(extra_dims)
         self.ncomp = int(ncomp)
         self.wire = wire
-        if wire is None:
+        self.keep = None
+        if keep is not None:
+            keep = list(keep)
+            nk = len(keep)
+            if nk != Pi.ndims:
+                raise ValueError(
+                    f"keep needs one (a, b) per logical dim: got {nk} for "
+                    f"{Pi.ndims} dims")
+            # None = the full range; the engine validates the values
+            self.keep = tuple(
+                (int(N), 0) if kd is None else (int(kd[0]), int(kd[1]))
+                for kd, N in zip(keep, Pi.size_global))
+            _check(lib, lib.pa_plan_create_keep(
+                self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
+                (I64 * e)(*extra_dims) if e else None, rank,
+                1 if aliased else 0,
+                (I64 * nk)(*[a for a, _ in self.keep]),
+                (I64 * nk)(*[b for _, b in self.keep]), int(fill),
+                ctypes.byref(self._plan)), "pa_plan_create_keep")
+        elif wire is None:
             _check(lib, lib.pa_plan_create_comp(
                 self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
                 (I64 * e)(*extra_dims) if e else None, rank,
@@ -329,6 +396,51 @@ class NativePlan:
         n = nd.value
         return (tuple(dims[:n]), tuple(sstr[:n]), soff.value,
                 tuple(dstr[:n]), doff.value)
+
+    # ---- truncated transposes (keep plans) ---------------------------
+
+    def plan_keep(self):
+        """``(keep, fill)`` of a keep plan (pa_plan_keep), else None."""
+        n = 8
+        lo, hi, fill = (I64 * n)(), (I64 * n)(), ctypes.c_int()
+        if not self.lib.pa_plan_keep(self._plan, lo, hi, ctypes.byref(fill)):
+            return None
+        nk = len(self.keep) if self.keep is not None else 0
+        return (tuple((int(lo[d]), int(hi[d])) for d in range(nk)),
+                int(fill.value))
+
+    def nsub(self, which: int, k: int = 0) -> int:
+        return int(self.lib.pa_plan_nsub(self._plan, which, k))
+
+    def copydesc_sub(self, n: int, f: int, which: int, k: int, s: int):
+        nd = I64()
+        dims = (I64 * 8)()
+        sstr = (I64 * 8)()
+        dstr = (I64 * 8)()
+        soff = I64()
+        doff = I64()
+        st = self.lib.pa_plan_copydesc_sub(
+            self._plan, n, f, which, k, s, ctypes.byref(nd), dims, sstr,
+            ctypes.byref(soff), dstr, ctypes.byref(doff))
+        if st != 0:
+            return None
+        m = nd.value
+        return (tuple(dims[:m]), tuple(sstr[:m]), soff.value,
+                tuple(dstr[:m]), doff.value)
+
+    def nfill(self) -> int:
+        return int(self.lib.pa_plan_nfill(self._plan))
+
+    def filldesc(self, i: int):
+        nd = I64()
+        dims = (I64 * 8)()
+        dstr = (I64 * 8)()
+        doff = I64()
+        _check(self.lib, self.lib.pa_plan_filldesc(
+            self._plan, i, ctypes.byref(nd), dims, dstr, ctypes.byref(doff)),
+            "pa_plan_filldesc")
+        m = nd.value
+        return (tuple(dims[:m]), tuple(dstr[:m]), doff.value)
 
     # ---- multi-field transposes (pa_*_many) ----------------------------
 
@@ -605,7 +717,8 @@ def _native_plan_for(plan, src, pair) -> NativePlan:
     if pair is None:
         return NativePlan(plan.Pi, plan.Po, plan.rank,
                           src.data.element_size(), plan.extra_dims,
-                          aliased=plan.aliased, ncomp=src.ncomp)
+                          aliased=plan.aliased, ncomp=src.ncomp,
+                          keep=plan.keep, fill=plan.fill)
     return NativePlan(plan.Pi, plan.Po, plan.rank, pair.stored.itemsize,
                       plan.extra_dims, aliased=plan.aliased,
                       ncomp=src.ncomp * pair.comps, wire=pair.code)

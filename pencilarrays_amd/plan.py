@@ -30,11 +30,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 from .pencil import (
     Pencil,
     Region,
+    range_intersect,
     region_intersect,
     region_lengths,
     region_nelem,
@@ -101,6 +102,10 @@ class PeerBlock:
     recv_offset: int            # element offset into recv staging buffer
     pack: Optional[CopyDesc]    # src parent -> send buffer (None if empty/self)
     unpack: Optional[CopyDesc]  # recv buffer -> dst parent (None if empty/self)
+    # keep plans (build_plan(keep=...)): one staging block per non-empty
+    # sub-box of the block; ``pack``/``unpack`` stay None
+    pack_subs: List["SubBlock"] = field(default_factory=list)
+    unpack_subs: List["SubBlock"] = field(default_factory=list)
 
 
 @dataclass
@@ -124,6 +129,15 @@ class TransposePlan:
     # of dst.
     self_pack: Optional[CopyDesc] = None    # src -> recv_buf tail
     self_unpack: Optional[CopyDesc] = None  # recv_buf tail -> dst
+    # truncated transposes (keep plans): the keep set as (a, b) per logical
+    # dim, the fill mode, and the sub-box tables that replace the single
+    # descriptors above (which stay None)
+    keep: Optional[Tuple[Tuple[int, int], ...]] = None
+    fill: int = 0
+    local_subs: List[CopyDesc] = field(default_factory=list)
+    self_pack_subs: List["SubBlock"] = field(default_factory=list)
+    self_unpack_subs: List["SubBlock"] = field(default_factory=list)
+    fills: List["FillDesc"] = field(default_factory=list)
 
     @property
     def subgroup_global_ranks(self) -> List[int]:
@@ -156,7 +170,13 @@ def _window_desc_src(p: Pencil, rank: int, region: Region,
 
 def build_plan(Pi: Pencil, Po: Pencil, rank: int,
                extra_dims: Tuple[int, ...] = (),
-               aliased: bool = False) -> TransposePlan:
+               aliased: bool = False, keep=None,
+               fill="zero") -> TransposePlan:
+    """``keep`` (a sequence of ``(a, b)`` per logical dim, ``None`` entries
+    meaning full) builds a truncated transpose: see :func:`build_keep_plan`.
+    Without it the tables are the ordinary ones and ``fill`` is ignored."""
+    if keep is not None:
+        return build_keep_plan(Pi, Po, rank, extra_dims, aliased, keep, fill)
     extra_dims = tuple(int(e) for e in extra_dims)
     R = Pi.transpose_dim(Po)  # validates compatibility
     n = Pi.ndims
@@ -301,6 +321,341 @@ def build_plan(Pi: Pencil, Po: Pencil, rank: int,
     assert irecv == length_recv_remote
     plan.recv_nelem_total = irecv + (length_self if aliased else 0)
     return plan
+
+
+# --------------------------------------------------------------------------
+# Truncated transposes: move only a kept product set of indices.
+#
+# A keep set is K = K_0 x ... x K_{N-1} over the logical dims with
+# K_d = [0, a_d) U [N_d - b_d, N_d): the low and the high wavenumbers of a
+# c2c dimension, or b = 0 for an r2c one.  Every block of the ordinary plan
+# (a peer's send region, a peer's recv region, the self block) is intersected
+# with K, which leaves up to 2^N sub-boxes; each non-empty sub-box is a
+# staging block of its own with an ordinary normalised CopyDesc.  Sender and
+# receiver derive the same sub-boxes from the same ranges, in the same order.
+# The reference has no such option (transpose! moves every element).
+# --------------------------------------------------------------------------
+
+FILL_NONE, FILL_ZERO = 0, 1
+
+
+@dataclass(frozen=True)
+class SubBlock:
+    """One sub-box of a block: its global region, its staging block
+    (``offset``, ``nelem`` in elements) and its descriptor."""
+    region: Region
+    offset: int
+    nelem: int
+    desc: CopyDesc
+
+
+@dataclass(frozen=True)
+class FillDesc:
+    """A destination-only window of the output parent:
+    ``dst[doffset + sum j_i * dstrides_i] = 0`` for j over ``dims``."""
+    dims: Tuple[int, ...]
+    dstrides: Tuple[int, ...]
+    doffset: int
+
+    @property
+    def nelem(self) -> int:
+        return math.prod(self.dims) if self.dims else 1
+
+
+def fill_code(fill) -> int:
+    """``"zero"``/1 -> FILL_ZERO, ``None``/``"none"``/0 -> FILL_NONE."""
+    if fill is None or fill == "none":
+        return FILL_NONE
+    if fill == "zero":
+        return FILL_ZERO
+    if isinstance(fill, int) and not isinstance(fill, bool) and \
+            fill in (FILL_NONE, FILL_ZERO):
+        return fill
+    raise ValueError(f"fill must be 'zero' or None/'none' (got {fill!r})")
+
+
+def normalize_keep(size_global: Sequence[int], keep) -> Tuple[Tuple[int, int], ...]:
+    """Validate a keep set against the global size; ``None`` entries mean
+    the full range ``(N_d, 0)``."""
+    keep = list(keep)
+    if len(keep) != len(size_global):
+        raise ValueError(
+            f"keep needs one (a, b) per logical dim: got {len(keep)} for "
+            f"{len(size_global)} dims")
+    out = []
+    for d, (kd, N) in enumerate(zip(keep, size_global)):
+        if kd is None:
+            out.append((int(N), 0))
+            continue
+        a, b = (int(v) for v in kd)
+        if a < 0 or b < 0 or a + b > N:
+            raise ValueError(
+                f"keep[{d}] = ({a}, {b}) must satisfy a, b >= 0 and "
+                f"a + b <= {N}")
+        out.append((a, b))
+    return tuple(out)
+
+
+def fourier_keep(size_global: Sequence[int], kmax,
+                 real_dim: Optional[int] = None):
+    """The usual keep set of a pseudo-spectral code: wavenumbers
+    ``|k_d| <= kmax_d``.  A c2c dim keeps ``a = kmax_d + 1`` low and
+    ``b = kmax_d`` high indices, the r2c dim ``real_dim`` (which stores only
+    ``k >= 0``) ``a = kmax_d + 1, b = 0``.  ``kmax`` is one int for every dim
+    or a sequence with ``None`` entries for untruncated dims."""
+    n = len(size_global)
+    if isinstance(kmax, int):
+        kmax = [kmax] * n
+    kmax = list(kmax)
+    if len(kmax) != n:
+        raise ValueError("kmax needs one entry per logical dim")
+    out = []
+    for d in range(n):
+        if kmax[d] is None:
+            out.append(None)
+            continue
+        k = int(kmax[d])
+        a, b = k + 1, (0 if d == real_dim else k)
+        if k < 0 or a + b > size_global[d]:
+            raise ValueError(
+                f"kmax[{d}] = {k} does not fit dimension {size_global[d]}")
+        out.append((a, b))
+    return out
+
+
+def _keep_ranges(a: int, b: int, N: int) -> List[Tuple[int, int]]:
+    """The ranges of K_d, low before high; adjacent ranges merge."""
+    if a + b >= N:
+        return [(0, N)]
+    return [(0, a), (N - b, N)]
+
+
+def _box_product(per_dim: List[List[Tuple[int, int]]]) -> List[Region]:
+    """Every combination of one range per dim, dim 0 varying fastest."""
+    out: List[Region] = [()]
+    for ranges in reversed(per_dim):
+        out = [(r,) + tail for tail in out for r in ranges]
+    return out
+
+
+def sub_boxes(region: Region, keep, size_global) -> List[Region]:
+    """The non-empty sub-boxes of ``region`` intersected with the keep set,
+    low range before high range, dim 0 varying fastest."""
+    per_dim = [[range_intersect(rg, kr) for kr in _keep_ranges(a, b, N)]
+               for rg, (a, b), N in zip(region, keep, size_global)]
+    return [box for box in _box_product(per_dim) if region_nelem(box) > 0]
+
+
+def fill_regions(keep, size_global) -> List[Region]:
+    """The complement of the keep set as disjoint global boxes: for
+    d = 0..N-1, (kept in dims < d) x (dropped range [a_d, N_d - b_d) of dim
+    d) x (everything in dims > d).  A kept factor with both a low and a high
+    range contributes both (low first, dim 0 fastest), so there are at most
+    N boxes when every b_d = 0."""
+    n = len(size_global)
+    out = []
+    for d in range(n):
+        a, b = keep[d]
+        if size_global[d] - b <= a:
+            continue
+        per_dim = ([_keep_ranges(*keep[j], size_global[j]) for j in range(d)]
+                   + [[(a, size_global[d] - b)]]
+                   + [[(0, size_global[j])] for j in range(d + 1, n)])
+        out.extend(_box_product(per_dim))
+    return out
+
+
+def _fill_desc(dims, strides, offset) -> FillDesc:
+    """Drop unit axes and merge contiguous ones (strides ascend already)."""
+    axes = [(dim, st) for dim, st in zip(dims, strides) if dim != 1]
+    if not axes:
+        return FillDesc((1,), (1,), offset)
+    merged = [axes[0]]
+    for dim, st in axes[1:]:
+        pdim, pst = merged[-1]
+        if st == pst * pdim:
+            merged[-1] = (pdim * dim, pst)
+        else:
+            merged.append((dim, st))
+    dims, st = zip(*merged)
+    return FillDesc(tuple(dims), tuple(st), offset)
+
+
+def build_keep_plan(Pi: Pencil, Po: Pencil, rank: int,
+                    extra_dims: Tuple[int, ...], aliased: bool, keep,
+                    fill="zero") -> TransposePlan:
+    """The plan of a truncated transpose.  Blocks, peers and their order are
+    those of :func:`build_plan`; every count and offset is in KEPT elements;
+    the single descriptors (``pack``, ``unpack``, ``local``, ``self_pack``,
+    ``self_unpack``) are None and the ``*_subs`` tables hold one descriptor
+    per non-empty sub-box.  ``fills`` lists the destination windows outside
+    the keep set when ``fill`` is zero."""
+    extra_dims = tuple(int(e) for e in extra_dims)
+    R = Pi.transpose_dim(Po)
+    n, E = Pi.ndims, len(extra_dims)
+    size = Pi.size_global
+    keep = normalize_keep(size, keep)
+    fcode = fill_code(fill)
+    pex = math.prod(extra_dims or (1,))
+
+    q_rel = perm_relative(Po.perm, Pi.perm)
+    q_full = tuple(q_rel) + tuple(n + i for i in range(E))
+    inv_q = perm_inv(q_full)
+    _, pst_o = _parent_strides(Po, rank, extra_dims)
+
+    plan = TransposePlan(
+        rank=rank, Pi=Pi, Po=Po, extra_dims=extra_dims, r_dim=R,
+        nproc_sub=1 if R is None else Pi.topology.dims[R], my_k=0,
+        aliased=aliased, keep=keep, fill=fcode)
+
+    def to_dst(buf_dims, box: Region, src_strides, src_offset) -> CopyDesc:
+        starts = tuple(lo for lo, _ in
+                       Po.to_local(rank, box, memory_order=True)) + (0,) * E
+        dstrides = tuple(pst_o[inv_q[j]] for j in range(n + E))
+        doffset = sum(starts[i] * pst_o[i] for i in range(n + E))
+        return normalize_desc(CopyDesc(buf_dims, src_strides, src_offset,
+                                       dstrides, doffset))
+
+    def pack_sub(box: Region, off: int) -> SubBlock:
+        sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
+        return SubBlock(box, off, region_nelem(box) * pex, normalize_desc(
+            CopyDesc(sdims, sst, soff, _colmajor_strides(sdims), off)))
+
+    def unpack_sub(box: Region, off: int) -> SubBlock:
+        bdims = perm_apply(Pi.perm, region_lengths(box)) + extra_dims
+        return SubBlock(box, off, region_nelem(box) * pex,
+                        to_dst(bdims, box, _colmajor_strides(bdims), off))
+
+    def local_sub(box: Region) -> CopyDesc:
+        sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
+        return to_dst(sdims, box, sst, soff)
+
+    def self_block(region: Region, off: int) -> int:
+        """Sub-boxes of the self block: fused, or staged at ``off``."""
+        for box in sub_boxes(region, keep, size):
+            if aliased:
+                ps = pack_sub(box, off)
+                plan.self_pack_subs.append(ps)
+                plan.self_unpack_subs.append(unpack_sub(box, off))
+                off += ps.nelem
+            else:
+                plan.local_subs.append(local_sub(box))
+        return off
+
+    if fcode == FILL_ZERO:
+        axes_o = Po.axes_for_rank(rank)
+        for box in fill_regions(keep, size):
+            box = region_intersect(box, axes_o)
+            if region_nelem(box) == 0 or pex == 0:
+                continue
+            loc = Po.to_local(rank, box, memory_order=True)
+            dims = tuple(hi - lo for lo, hi in loc) + extra_dims
+            off = sum(lo * pst_o[i] for i, (lo, _) in enumerate(loc))
+            plan.fills.append(_fill_desc(dims, pst_o, off))
+
+    if R is None:
+        plan.recv_nelem_total = self_block(Pi.axes_for_rank(rank), 0)
+        return plan
+
+    topo = Pi.topology
+    coords = topo.cart_coords(rank)
+    plan.my_k = coords[R]
+    axes_local_i = Pi.axes_for_rank(rank)
+    axes_local_o = Po.axes_for_rank(rank)
+    isend = irecv = 0
+    for k in range(topo.dims[R]):
+        pc = list(coords)
+        pc[R] = k
+        pc = tuple(pc)
+        srange = region_intersect(axes_local_i, Po.axes_for_coords(pc))
+        rrange = region_intersect(axes_local_o, Pi.axes_for_coords(pc))
+        blk = PeerBlock(
+            peer_k=k, global_rank=topo.cart_rank(pc), send_region=srange,
+            recv_region=rrange, send_nelem=0, recv_nelem=0, send_offset=0,
+            recv_offset=0, pack=None, unpack=None)
+        sboxes = sub_boxes(srange, keep, size)
+        rboxes = sub_boxes(rrange, keep, size)
+        blk.send_nelem = sum(region_nelem(b) for b in sboxes) * pex
+        blk.recv_nelem = sum(region_nelem(b) for b in rboxes) * pex
+        if k != plan.my_k:
+            blk.send_offset, blk.recv_offset = isend, irecv
+            for box in sboxes:
+                blk.pack_subs.append(pack_sub(box, isend))
+                isend += blk.pack_subs[-1].nelem
+            for box in rboxes:
+                blk.unpack_subs.append(unpack_sub(box, irecv))
+                irecv += blk.unpack_subs[-1].nelem
+        plan.peers.append(blk)
+    plan.send_nelem_total = isend
+    self_blk = plan.peers[plan.my_k]
+    self_blk.recv_offset = irecv  # the self block sits at the recv tail
+    plan.recv_nelem_total = self_block(self_blk.send_region, irecv)
+    return plan
+
+
+def nsub(plan: TransposePlan, which: int, k: int = 0) -> int:
+    """Sub-boxes behind ``which`` (as in :func:`copydesc_many`) of a keep
+    plan; peer ``k`` for packs and unpacks."""
+    if plan.keep is None:
+        raise ValueError("not a keep plan")
+    if which == 0:
+        return len(plan.local_subs)
+    if which in (3, 4):
+        return len(plan.self_pack_subs)
+    if plan.r_dim is None or not 0 <= k < len(plan.peers):
+        return 0
+    if which == 1:
+        return len(plan.peers[k].pack_subs)
+    if which == 2:
+        return len(plan.peers[k].unpack_subs)
+    raise ValueError(f"bad which {which}")
+
+
+def copydesc_sub(plan: TransposePlan, n: int, f: int, which: int, k: int,
+                 s: int) -> Optional[CopyDesc]:
+    """Sub-box ``s`` of field ``f`` of ``n`` on a keep plan, ``which`` as in
+    :func:`copydesc_many`.  The multi-field rule holds per sub-box: field
+    ``f`` sits at ``n*o_s + f*c_s``."""
+    _check_many(n, f)
+    if not 0 <= s < nsub(plan, which, k):
+        return None
+    if which == 0:
+        return plan.local_subs[s]
+    if which == 1:
+        sb = plan.peers[k].pack_subs[s]
+    elif which == 2:
+        sb = plan.peers[k].unpack_subs[s]
+    elif which == 3:
+        sb = plan.self_pack_subs[s]
+    else:
+        sb = plan.self_unpack_subs[s]
+    d, sh = sb.desc, many_shift(n, f, sb.offset, sb.nelem)
+    if which in (1, 3):
+        return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
+                        d.doffset + sh)
+    return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides, d.doffset)
+
+
+def stage_descs(plan: TransposePlan, n: int, f: int, stage: int):
+    """``(which, desc)`` for every copy that ``stage`` (0 pack, 1 local,
+    2 unpack) runs for field ``f`` of ``n`` on a keep plan, in launch order."""
+    out = []
+    if stage == 0:
+        for blk in plan.peers:
+            for s in range(len(blk.pack_subs)):
+                out.append((1, copydesc_sub(plan, n, f, 1, blk.peer_k, s)))
+        for s in range(len(plan.self_pack_subs)):
+            out.append((3, copydesc_sub(plan, n, f, 3, 0, s)))
+    elif stage == 1:
+        for d in plan.local_subs:
+            out.append((0, d))
+        for s in range(len(plan.self_unpack_subs)):
+            out.append((4, copydesc_sub(plan, n, f, 4, 0, s)))
+    else:
+        for blk in plan.peers:
+            for s in range(len(blk.unpack_subs)):
+                out.append((2, copydesc_sub(plan, n, f, 2, blk.peer_k, s)))
+    return out
 
 
 # --------------------------------------------------------------------------

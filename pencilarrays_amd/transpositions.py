@@ -25,10 +25,11 @@ from typing import Sequence
 import numpy as np
 
 from .array import PencilArray
-from .copyexec import apply_copy, apply_copy_conv
+from .copyexec import apply_copy, apply_copy_conv, apply_fill
 from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
-                   copydesc_many, peer_message)
+                   copydesc_many, peer_message, stage_descs)
+from .plan import fourier_keep  # noqa: F401  (the keep-set helper, re-exported)
 from .wire import narrow, resolve_wire, widen
 
 MPI_TAG = 42  # Transpositions.jl:469
@@ -54,6 +55,13 @@ def _wire_pair(dest: PencilArray, src: PencilArray, wire_dtype):
             f"a reduced-precision wire needs dest and src of one dtype: "
             f"{dest.data.dtype} != {src.data.dtype}")
     return pair
+
+
+def _check_keep_wire(keep, wire_dtype):
+    if keep is not None and wire_dtype is not None:
+        raise ValueError(
+            "keep together with wire_dtype is not supported: a truncated "
+            "transpose moves the stored type")
 
 
 def _wire_convs(pair):
@@ -83,8 +91,16 @@ def _arrays_alias(a, b) -> bool:
 
 class Transposition:
     def __init__(self, dest: PencilArray, src: PencilArray,
-                 method: str = "grouped", wire_dtype=None):
+                 method: str = "grouped", wire_dtype=None, keep=None,
+                 fill="zero"):
         """``Transposition(Ao, Ai; method)`` (Transpositions.jl:94-119).
+
+        ``keep`` (``(a, b)`` per logical dim, ``None`` entries meaning full;
+        see :func:`fourier_keep`) makes this a truncated transpose: only
+        global indices with ``i_d < a_d`` or ``i_d >= N_d - b_d`` in every
+        dim move, bit for bit; the rest of ``dest`` becomes +0 with
+        ``fill="zero"`` and is left untouched with ``fill=None``
+        (pa_plan_create_keep).  Not available together with ``wire_dtype``.
 
         ``wire_dtype`` (``"float32"``, ``"float16"``, ``"bfloat16"``, or the
         numpy / torch dtype) sends the data in that narrower real scalar type:
@@ -112,6 +128,7 @@ class Transposition:
             raise ValueError("dest and src must live on the same rank")
         if method not in ("grouped", "point_to_point", "alltoallv"):
             raise ValueError(f"unknown transpose method {method!r}")
+        _check_keep_wire(keep, wire_dtype)
         self.method = method
         self.wire = _wire_pair(dest, src, wire_dtype)
         self.src = src
@@ -119,7 +136,7 @@ class Transposition:
         self.aliased = _arrays_alias(src.data, dest.data)
         self.plan: TransposePlan = build_plan(
             src.pencil, dest.pencil, src.rank, src.extra_dims,
-            aliased=self.aliased)
+            aliased=self.aliased, keep=keep, fill=fill)
         self._native = None  # set lazily for the GPU path
 
     # ------------------------------------------------------------------
@@ -129,6 +146,8 @@ class Transposition:
     def _execute_numpy(self, use_dist: bool):
         if self.wire is not None:
             return self._execute_numpy_wire(use_dist)
+        if self.plan.keep is not None:
+            return self._execute_numpy_keep(use_dist)
         plan = self.plan
         # vector-valued elements: one opaque B-byte item per element, so the
         # element-unit descriptors apply unchanged
@@ -204,6 +223,60 @@ class Transposition:
         for blk in plan.peers:
             if blk.unpack is not None:
                 apply_copy(blk.unpack, recv_buf, dst_flat)
+
+    def _execute_numpy_keep(self, use_dist: bool):
+        """The same stages on a keep plan: one copy per sub-box, messages of
+        the kept elements only, and the zero fill next to the local copy."""
+        plan = self.plan
+        src_flat = self.src.element_view()
+        dst_flat = self.dest.element_view()
+        send_buf = np.empty(plan.send_nelem_total, dtype=src_flat.dtype)
+        recv_buf = np.empty(plan.recv_nelem_total, dtype=src_flat.dtype)
+
+        # every pack (and staged self pack) before any write of dst
+        for which, d in stage_descs(plan, 1, 0, 0):
+            apply_copy(d, src_flat, send_buf if which == 1 else recv_buf)
+
+        reqs = []
+        msgs = [blk for blk in plan.peers if blk.peer_k != plan.my_k
+                and (blk.send_nelem or blk.recv_nelem)]
+        if msgs:
+            if not use_dist:
+                raise RuntimeError(
+                    "distributed transpose requires torch.distributed to be "
+                    "initialised (or use run_transpose_sim for in-process "
+                    "tests)")
+            import torch.distributed as dist
+            topo = plan.Pi.topology
+            if dist.get_world_size() != topo.nranks:
+                raise RuntimeError(
+                    f"torch.distributed world size {dist.get_world_size()} "
+                    f"!= topology nranks {topo.nranks}")
+            if dist.get_rank() != plan.rank:
+                raise RuntimeError(
+                    f"torch.distributed rank {dist.get_rank()} != topology "
+                    f"rank {plan.rank}")
+            # a peer with nothing kept is absent from the exchange
+            for blk in msgs:
+                if blk.recv_nelem > 0:
+                    rt = _wire(recv_buf[
+                        blk.recv_offset:blk.recv_offset + blk.recv_nelem])
+                    reqs.append(dist.irecv(rt, src=blk.global_rank,
+                                           tag=MPI_TAG))
+                if blk.send_nelem > 0:
+                    st = _wire(send_buf[
+                        blk.send_offset:blk.send_offset + blk.send_nelem])
+                    reqs.append(dist.isend(st, dst=blk.global_rank,
+                                           tag=MPI_TAG))
+
+        for which, d in stage_descs(plan, 1, 0, 1):
+            apply_copy(d, src_flat if which == 0 else recv_buf, dst_flat)
+        for fd in plan.fills:
+            apply_fill(fd, dst_flat)
+        for r in reqs:
+            r.wait()
+        for _, d in stage_descs(plan, 1, 0, 2):
+            apply_copy(d, recv_buf, dst_flat)
 
     def _execute_numpy_wire(self, use_dist: bool):
         """The same stages with a reduced-precision wire: staging buffers of
@@ -309,12 +382,13 @@ class Transposition:
 
 
 def transpose_into(dest: PencilArray, src: PencilArray,
-                   method: str = "grouped", wire_dtype=None) -> PencilArray:
+                   method: str = "grouped", wire_dtype=None, keep=None,
+                   fill="zero") -> PencilArray:
     """``transpose!(dest, src; method)`` (Transpositions.jl:161-169)."""
     if dest is src:
         return dest
-    return Transposition(dest, src, method=method,
-                         wire_dtype=wire_dtype).execute()
+    return Transposition(dest, src, method=method, wire_dtype=wire_dtype,
+                         keep=keep, fill=fill).execute()
 
 
 class MultiTransposition:
@@ -335,10 +409,13 @@ class MultiTransposition:
     field, which pins the semantics, not the performance.
 
     ``wire_dtype``: a reduced-precision wire for every field, as in
-    :class:`Transposition`."""
+    :class:`Transposition`.  ``keep`` / ``fill``: a truncated transpose of
+    every field, as in :class:`Transposition`."""
 
     def __init__(self, dests: Sequence[PencilArray],
-                 srcs: Sequence[PencilArray], wire_dtype=None):
+                 srcs: Sequence[PencilArray], wire_dtype=None, keep=None,
+                 fill="zero"):
+        _check_keep_wire(keep, wire_dtype)
         dests, srcs = list(dests), list(srcs)
         if len(dests) != len(srcs):
             raise ValueError(
@@ -387,12 +464,13 @@ class MultiTransposition:
         self.srcs = srcs
         self.dests = dests
         self.wire_dtype = wire_dtype
+        self.keep, self.fill = keep, fill
         self.wire = _wire_pair(d0, s0, wire_dtype)
         self.aliased = any(_arrays_alias(s.data, d.data)
                            for s in srcs for d in dests)
         self.plan: TransposePlan = build_plan(
             s0.pencil, d0.pencil, s0.rank, s0.extra_dims,
-            aliased=self.aliased)
+            aliased=self.aliased, keep=keep, fill=fill)
         self._native = None
 
     def _execute_numpy(self):
@@ -405,7 +483,8 @@ class MultiTransposition:
         else:
             srcs = self.srcs
         for d, s in zip(self.dests, srcs):
-            Transposition(d, s, wire_dtype=self.wire_dtype).execute()
+            Transposition(d, s, wire_dtype=self.wire_dtype, keep=self.keep,
+                          fill=self.fill).execute()
 
     def execute(self, sync: bool = True):
         """Run the transposes; ``sync=False`` returns with the work enqueued
@@ -434,9 +513,11 @@ class MultiTransposition:
 
 
 def transpose_many_into(dests: Sequence[PencilArray],
-                        srcs: Sequence[PencilArray], wire_dtype=None):
+                        srcs: Sequence[PencilArray], wire_dtype=None,
+                        keep=None, fill="zero"):
     """``transpose!`` of every pair ``dests[i] <- srcs[i]`` in one call."""
-    return MultiTransposition(dests, srcs, wire_dtype=wire_dtype).execute()
+    return MultiTransposition(dests, srcs, wire_dtype=wire_dtype, keep=keep,
+                              fill=fill).execute()
 
 
 # ----------------------------------------------------------------------
@@ -447,14 +528,19 @@ def transpose_many_into(dests: Sequence[PencilArray],
 
 def run_transpose_sim(dests: Sequence[PencilArray],
                       srcs: Sequence[PencilArray],
-                      staging_out=None, wire_dtype=None) -> None:
+                      staging_out=None, wire_dtype=None, keep=None,
+                      fill="zero") -> None:
     """``staging_out``, if a dict, receives the final ``send``/``recv``
     staging buffers per rank.  ``wire_dtype``: a reduced-precision wire (see
-    :class:`Transposition`); the staging buffers then hold wire scalars."""
-    if wire_dtype is not None:
+    :class:`Transposition`); the staging buffers then hold wire scalars.
+    ``keep`` / ``fill``: a truncated transpose (see :class:`Transposition`);
+    the staging buffers then hold the kept elements only."""
+    _check_keep_wire(keep, wire_dtype)
+    if wire_dtype is not None or keep is not None:
         return run_transpose_sim_many([[d] for d in dests],
                                       [[s] for s in srcs], staging_out,
-                                      wire_dtype=wire_dtype)
+                                      wire_dtype=wire_dtype, keep=keep,
+                                      fill=fill)
     nranks = len(srcs)
     plans = [build_plan(s.pencil, d.pencil, r, s.extra_dims,
                         aliased=_arrays_alias(s.data, d.data))
@@ -512,7 +598,8 @@ def run_transpose_sim(dests: Sequence[PencilArray],
 
 def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
-                           staging_out=None, wire_dtype=None) -> None:
+                           staging_out=None, wire_dtype=None, keep=None,
+                           fill="zero") -> None:
     """:func:`run_transpose_sim` for ``n`` fields per rank with the
     multi-field staging layout (plan.py): every field of a rank is packed
     into ONE n-fold send buffer, and the exchange is ONE slice copy per peer
@@ -522,10 +609,15 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
     ``send``/``recv`` buffers per rank (tests compare them).
     ``wire_dtype``: a reduced-precision wire; the staging buffers then hold
     wire scalars (bfloat16 as uint16 patterns), packs narrow, unpacks widen
-    and the local copy rounds."""
+    and the local copy rounds.  ``keep`` / ``fill``: a truncated transpose
+    through the sub-box tables of the keep plan."""
+    _check_keep_wire(keep, wire_dtype)
     if wire_dtype is not None:
         return _run_sim_many_wire(dests_per_rank, srcs_per_rank, staging_out,
                                   wire_dtype)
+    if keep is not None:
+        return _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out,
+                                  keep, fill)
     nranks = len(srcs_per_rank)
     n = len(srcs_per_rank[0])
     if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
@@ -586,6 +678,70 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                 if blk.unpack is not None:
                     apply_copy(copydesc_many(p, n, f, 2, blk.peer_k),
                                recv_bufs[r], dflat[r][f])
+    if staging_out is not None:
+        staging_out["send"] = send_bufs
+        staging_out["recv"] = recv_bufs
+
+
+def _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out, keep,
+                       fill) -> None:
+    """run_transpose_sim_many on keep plans: the same stages over the
+    sub-box tables, one slice copy of the KEPT elements per peer pair (none
+    for a peer with nothing kept), and the zero fill of every field."""
+    nranks = len(srcs_per_rank)
+    n = len(srcs_per_rank[0])
+    if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
+            any(len(x) != n for x in dests_per_rank):
+        raise ValueError("every rank needs the same number (>= 1) of fields")
+    plans = []
+    for r in range(nranks):
+        s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
+        if d0.elem_dims != s0.elem_dims:
+            raise ValueError(
+                f"incompatible element dimensions of PencilArrays: "
+                f"{s0.elem_dims} != {d0.elem_dims}")
+        aliased = any(_arrays_alias(s.data, d.data)
+                      for s in srcs_per_rank[r] for d in dests_per_rank[r])
+        plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
+                                aliased=aliased, keep=keep, fill=fill))
+    sflat = [[s.element_view() for s in row] for row in srcs_per_rank]
+    dflat = [[d.element_view() for d in row] for row in dests_per_rank]
+    dt = sflat[0][0].dtype
+    send_bufs, recv_bufs = [], []
+    for p in plans:
+        ns, nr = buffer_nelem_many(p, n)
+        send_bufs.append(np.empty(ns, dtype=dt))
+        recv_bufs.append(np.empty(nr, dtype=dt))
+
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for which, d in stage_descs(p, n, f, 0):
+                apply_copy(d, sflat[r][f],
+                           send_bufs[r] if which == 1 else recv_bufs[r])
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for which, d in stage_descs(p, n, f, 1):
+                apply_copy(d, sflat[r][f] if which == 0 else recv_bufs[r],
+                           dflat[r][f])
+            for fd in p.fills:
+                apply_fill(fd, dflat[r][f])
+
+    for r, p in enumerate(plans):
+        if p.r_dim is None:
+            continue
+        for blk in p.peers:
+            if blk.peer_k == p.my_k or blk.send_nelem == 0:
+                continue
+            so, sn, _, _ = peer_message(p, n, blk.peer_k)
+            q = plans[blk.global_rank]
+            _, _, ro, rn = peer_message(q, n, p.my_k)
+            assert rn == sn, (r, blk.peer_k, sn, rn)
+            recv_bufs[blk.global_rank][ro:ro + rn] = send_bufs[r][so:so + sn]
+
+    for r, p in enumerate(plans):
+        for f in range(n):
+            for _, d in stage_descs(p, n, f, 2):
+                apply_copy(d, recv_bufs[r], dflat[r][f])
     if staging_out is not None:
         staging_out["send"] = send_bufs
         staging_out["recv"] = recv_bufs
