@@ -354,6 +354,12 @@ pa_status pa_plan_filldesc(const pa_plan *p, int i, int64_t *nd,
  * the same arrays leaves it unchanged — nothing was built or allocated. */
 int pa_plan_stage_table_count(const pa_plan *p);
 
+/* Stage tables this plan has built since it was created, evicted and dropped
+ * ones included.  At the cache's capacity a build replaces a table and leaves
+ * pa_plan_stage_table_count() unchanged; this counter still moves, so a call
+ * that leaves it unchanged was served from the cache. */
+int64_t pa_plan_stage_table_builds(const pa_plan *p);
+
 /* ---- reductions (src/reductions.jl:9-38) ----------------------------- */
 /* One ncclAllReduce over a communicator (normally the FULL topology comm):
  * the collective behind the reference's mapreduce/any/all.

@@ -2066,6 +2066,7 @@ struct pa_plan {
      * keyed on (n, stage, every pointer the stage touches) */
     std::vector<StageTable *> tables;
     uint64_t table_clock = 0;
+    int64_t table_builds = 0; /* tables ever built (pa_plan_stage_table_builds) */
     /* truncated transpose (pa_plan_create_keep): K_d = [0, keep_lo[d]) U
      * [N_d - keep_hi[d], N_d) per logical dim.  Every count and offset above
      * is then in KEPT elements, the single descriptors are unset and the
@@ -3878,6 +3879,7 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
         if (!st) st = upload_stage(t);
         if (st) { free_table(t); return st; }
         p->tables.push_back(t);
+        p->table_builds++;
     }
     t->stamp = ++p->table_clock;
     for (auto &l : t->launches) {
@@ -3981,6 +3983,11 @@ pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
 int pa_plan_stage_table_count(const pa_plan *p)
 {
     return p ? (int)p->tables.size() : 0;
+}
+
+int64_t pa_plan_stage_table_builds(const pa_plan *p)
+{
+    return p ? p->table_builds : 0;
 }
 
 /* ---- truncated transposes: introspection and the stand-alone fill ---- */

@@ -44,6 +44,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     lib.pa_last_error.restype = ctypes.c_char_p
     lib.pa_pencil_length_local.restype = I64
+    lib.pa_plan_stage_table_builds.restype = I64
     _LIB = lib
     return lib
 
@@ -494,6 +495,11 @@ class NativePlan:
     def stage_table_count(self) -> int:
         """Stage tables in the plan's cache (pa_plan_stage_table_count)."""
         return int(self.lib.pa_plan_stage_table_count(self._plan))
+
+    def stage_table_builds(self) -> int:
+        """Stage tables built so far, evicted ones included
+        (pa_plan_stage_table_builds)."""
+        return int(self.lib.pa_plan_stage_table_builds(self._plan))
 
     def copydesc_many(self, n: int, f: int, which: int, k: int = 0):
         nd = I64()
