@@ -1988,8 +1988,10 @@ struct pa_comm {
 
 /* ================= plan ============================================ */
 
-/* one sub-box of a block on a keep plan: its staging block (offset and
- * count in elements) and its descriptor */
+/* one sub-block of a block: its staging block (offset and count in
+ * elements) and its descriptor.  Under a keep set a block has one per
+ * non-empty sub-box; on an ordinary plan, whose keep set is everything, it
+ * has at most one, the block itself. */
 struct SubC {
     int64_t off, n;
     CopyDescH d;
@@ -1997,18 +1999,16 @@ struct SubC {
 
 struct PeerBlockC {
     int k, grank;
-    int64_t send_off, recv_off, send_n, recv_n;
-    bool has_pack = false, has_unpack = false;
-    CopyDescH pack, unpack;
-    /* chunked-exchange support: the send/recv blocks viewed as
-     * (rowelems x outer) with outer = the last raw (Pi-mem-order + extras)
-     * axis — identical split on sender and receiver by construction. */
+    int64_t send_off = 0, recv_off = 0, send_n = 0, recv_n = 0;
+    std::vector<SubC> pack, unpack;
+    /* chunked-exchange support (ordinary plans, one sub-block): the
+     * send/recv blocks viewed as (rowelems x outer) with outer = the last
+     * raw (Pi-mem-order + extras) axis — identical split on sender and
+     * receiver by construction. */
     int64_t send_outer = 1, send_rowelems = 0;
     int64_t recv_outer = 1, recv_rowelems = 0;
     CopyDescH unpack_raw; /* un-normalized: nd = n+E, axis nd-1 = outer */
     bool has_unpack_raw = false;
-    /* keep plans: one staging block per non-empty sub-box of the block */
-    std::vector<SubC> pack_subs, unpack_subs;
 };
 
 struct StageTable; /* multi-field stage: launch list + device tables */
@@ -2030,13 +2030,11 @@ struct pa_plan {
     int P;    /* subgroup size */
     int myk;  /* my coordinate along R */
     std::vector<PeerBlockC> peers;
-    bool has_local = false;
-    CopyDescH local;
-    /* aliased (in-place) mode: self block staged through the recv tail
-     * (Transpositions.jl:250-264, :394-404) */
+    /* the self block: fused src-window -> dst-window copies (`local`, no
+     * staging block: off = n = 0), or in aliased (in-place) mode staged
+     * through the recv tail (Transpositions.jl:250-264, :394-404) */
     bool aliased = false;
-    bool has_self = false;
-    CopyDescH self_pack, self_unpack;
+    std::vector<SubC> local, self_pack, self_unpack;
     int64_t send_total = 0, recv_total = 0; /* elements (remote blocks) */
     void *send_buf = nullptr, *recv_buf = nullptr;
     bool own_bufs = false;
@@ -2069,14 +2067,12 @@ struct pa_plan {
     int64_t table_builds = 0; /* tables ever built (pa_plan_stage_table_builds) */
     /* truncated transpose (pa_plan_create_keep): K_d = [0, keep_lo[d]) U
      * [N_d - keep_hi[d], N_d) per logical dim.  Every count and offset above
-     * is then in KEPT elements, the single descriptors are unset and the
-     * sub-box tables below take their place; fills lists the destination
-     * windows outside the keep set (PA_FILL_ZERO). */
+     * is then in KEPT elements and a block holds one sub-block per non-empty
+     * sub-box; fills lists the destination windows outside the keep set
+     * (PA_FILL_ZERO). */
     bool keep = false;
     int fill = PA_FILL_NONE;
     std::vector<int64_t> keep_lo, keep_hi;
-    std::vector<CopyDescH> local_subs;
-    std::vector<SubC> self_pack_subs, self_unpack_subs;
     std::vector<FillDescH> fills;
 };
 
@@ -2145,23 +2141,10 @@ static void window_desc(const pa_pencil &p, int rank,
 /* buffer->dest unpack descriptor: buffer axes = Pi memory order (+extras),
  * column-major with given strides; dest axis i' reads buffer axis
  * inv(perm_i)[perm_o[i']] (the relative permutation, Transpositions.jl:506).
- */
-static CopyDescH unpack_desc_raw_out(const pa_plan &pl, const Range *grange,
-                                     const int64_t *bufdims,
-                                     const int64_t *bufstr, int64_t bufoff,
-                                     CopyDescH *raw_out);
-
+ * raw_out, if given, receives the same copy un-normalized. */
 static CopyDescH unpack_desc(const pa_plan &pl, const Range *grange,
                              const int64_t *bufdims, const int64_t *bufstr,
-                             int64_t bufoff)
-{
-    return unpack_desc_raw_out(pl, grange, bufdims, bufstr, bufoff, nullptr);
-}
-
-static CopyDescH unpack_desc_raw_out(const pa_plan &pl, const Range *grange,
-                                     const int64_t *bufdims,
-                                     const int64_t *bufstr, int64_t bufoff,
-                                     CopyDescH *raw_out)
+                             int64_t bufoff, CopyDescH *raw_out = nullptr)
 {
     const pa_pencil &Po = pl.Po;
     const pa_pencil &Pi = pl.Pi;
@@ -2198,37 +2181,6 @@ static CopyDescH unpack_desc_raw_out(const pa_plan &pl, const Range *grange,
         for (int i = 0; i < n + E; i++) raw_out->total *= bufdims[i];
     }
     return normalize_desc(n + E, bufdims, bufstr, bufoff, dstr, doff);
-}
-
-
-/* staged self block (aliased mode): pack src window -> recv tail, unpack
- * recv tail -> dst window */
-static void staged_self_descs(pa_plan *pl, const Range *sr, const Range *rr,
-                              int64_t recv_off)
-{
-    const pa_pencil &Pi = pl->Pi;
-    const int n = Pi.n, e = pl->E;
-    int64_t dims[2 * MAXND], str[2 * MAXND], off;
-    int kk;
-    window_desc(Pi, pl->rank, pl->extra, sr, dims, str, &off, &kk);
-    int64_t cstr[2 * MAXND], acc = 1;
-    for (int i = 0; i < kk; i++) {
-        cstr[i] = acc;
-        acc *= dims[i];
-    }
-    pl->self_pack = normalize_desc(kk, dims, str, off, cstr, recv_off);
-    int64_t bdims[2 * MAXND];
-    for (int i = 0; i < n; i++)
-        bdims[i] = rr[Pi.perm[i]].hi - rr[Pi.perm[i]].lo;
-    for (int e2 = 0; e2 < e; e2++) bdims[n + e2] = pl->extra[e2];
-    int64_t bstr[2 * MAXND];
-    acc = 1;
-    for (int i = 0; i < n + e; i++) {
-        bstr[i] = acc;
-        acc *= bdims[i];
-    }
-    pl->self_unpack = unpack_desc(*pl, rr, bdims, bstr, recv_off);
-    pl->has_self = true;
 }
 
 
@@ -2287,14 +2239,27 @@ static void box_product(int n, const std::vector<Range> *per_dim,
     }
 }
 
+/* The sub-boxes of a block.  Under a keep set: the non-empty intersections of
+ * its region with K.  On an ordinary plan K is everything, so the region
+ * itself, gated as ordinary plans always were: a block of a subgroup on its
+ * element count, extras included, and the same-decomposition block (R < 0)
+ * on its geometry alone. */
 static void sub_boxes(const pa_plan &pl, const Range *region,
                       std::vector<Box> *out)
 {
+    const int n = pl.Pi.n;
+    if (!pl.keep) {
+        Box b;
+        memcpy(b.r, region, sizeof(Range) * n);
+        if (region_nelem(n, region) * (pl.R < 0 ? 1 : prod_extra(pl)) > 0)
+            out->push_back(b);
+        return;
+    }
     std::vector<Range> per_dim[MAXND];
-    for (int d = 0; d < pl.Pi.n; d++)
+    for (int d = 0; d < n; d++)
         per_dim[d] = keep_ranges(pl.keep_lo[d], pl.keep_hi[d],
                                  pl.Pi.size_global[d]);
-    box_product(pl.Pi.n, per_dim, region, out);
+    box_product(n, per_dim, region, out);
 }
 
 static int64_t box_nelem(const pa_plan &pl, const Box &b)
@@ -2317,8 +2282,10 @@ static SubC pack_sub(const pa_plan &pl, const Box &b, int64_t off)
                 normalize_desc(kk, dims, str, woff, cstr, off)};
 }
 
-/* unpack of a box: staging block at `off` (Pi memory order) -> dst window */
-static SubC unpack_sub(const pa_plan &pl, const Box &b, int64_t off)
+/* unpack of a box: staging block at `off` (Pi memory order) -> dst window;
+ * raw_out as in unpack_desc */
+static SubC unpack_sub(const pa_plan &pl, const Box &b, int64_t off,
+                       CopyDescH *raw_out = nullptr)
 {
     const int n = pl.Pi.n, e = pl.E;
     int64_t bdims[2 * MAXND], bstr[2 * MAXND], acc = 1;
@@ -2329,31 +2296,32 @@ static SubC unpack_sub(const pa_plan &pl, const Box &b, int64_t off)
         bstr[i] = acc;
         acc *= bdims[i];
     }
-    return SubC{off, box_nelem(pl, b), unpack_desc(pl, b.r, bdims, bstr, off)};
+    return SubC{off, box_nelem(pl, b),
+                unpack_desc(pl, b.r, bdims, bstr, off, raw_out)};
 }
 
-/* fused local copy of a box: src window -> dst window */
-static CopyDescH local_sub(const pa_plan &pl, const Box &b)
+/* fused local copy of a box: src window -> dst window, no staging block */
+static SubC local_sub(const pa_plan &pl, const Box &b)
 {
     int64_t dims[2 * MAXND], str[2 * MAXND], off;
     int kk;
     window_desc(pl.Pi, pl.rank, pl.extra, b.r, dims, str, &off, &kk);
-    return unpack_desc(pl, b.r, dims, str, off);
+    return SubC{0, 0, unpack_desc(pl, b.r, dims, str, off)};
 }
 
-/* the self block under the keep set: fused copies, or in aliased mode staged
- * through the recv buffer from element offset `off`; returns the end offset */
-static int64_t keep_self_block(pa_plan *pl, const Range *region, int64_t off)
+/* the self block: fused copies, or in aliased mode staged through the recv
+ * buffer from element offset `off`; returns the end offset */
+static int64_t self_block(pa_plan *pl, const Range *region, int64_t off)
 {
     std::vector<Box> boxes;
     sub_boxes(*pl, region, &boxes);
     for (auto &b : boxes) {
         if (pl->aliased) {
-            pl->self_pack_subs.push_back(pack_sub(*pl, b, off));
-            pl->self_unpack_subs.push_back(unpack_sub(*pl, b, off));
+            pl->self_pack.push_back(pack_sub(*pl, b, off));
+            pl->self_unpack.push_back(unpack_sub(*pl, b, off));
             off += box_nelem(*pl, b);
         } else
-            pl->local_subs.push_back(local_sub(*pl, b));
+            pl->local.push_back(local_sub(*pl, b));
     }
     return off;
 }
@@ -2398,6 +2366,280 @@ static void keep_fills(pa_plan *pl)
             pl->fills.push_back(normalize_fill(n + pl->E, dims, pst_o, off));
         }
     }
+}
+
+/* the last raw axis (Pi memory order + extras) of a block: the axis a chunked
+ * exchange splits */
+static int64_t outer_extent(const pa_plan &pl, const Range *region)
+{
+    if (pl.E) return pl.extra[pl.E - 1];
+    const Range &r = region[pl.Pi.perm[pl.Pi.n - 1]];
+    return r.hi - r.lo;
+}
+
+/* The one plan builder.  keep_lo/keep_hi null: an ordinary plan, every block
+ * at most one sub-block; else the plan of a truncated transpose with `fill`.
+ * Peers, their order and the staging layout are the same either way. */
+static pa_status plan_build(const pa_pencil *pin, const pa_pencil *pout,
+                            int64_t scalar_size, int64_t ncomp, int e,
+                            const int64_t *extra_dims, int rank, int flags,
+                            const int64_t *keep_lo, const int64_t *keep_hi,
+                            int fill, pa_plan **out)
+{
+    /* assert_compatible (Transpositions.jl:182-199) */
+    if (pin->topo.m != pout->topo.m || pin->topo.dims != pout->topo.dims)
+        return fail("pencil topologies must be the same.");
+    if (pin->n != pout->n || pin->size_global != pout->size_global)
+        return fail("global data sizes must be the same between different "
+                    "pencil configurations.");
+    int ndiff = 0, R = -1;
+    for (int j = 0; j < pin->topo.m; j++)
+        if (pin->decomp[j] != pout->decomp[j]) {
+            ndiff++;
+            if (R < 0) R = j;
+        }
+    if (ndiff > 1)
+        return fail("pencil decompositions must differ in at most one "
+                    "dimension.");
+    if (rank < 0 || rank >= pin->topo.nranks) return fail("rank out of range");
+    if (pa_status cst = check_comp(scalar_size, ncomp)) return cst;
+    if (pin->n + e > MAXND)
+        return fail("too many dims: N+E must be <= %d", MAXND);
+
+    const int n = pin->n;
+    auto *pl = new pa_plan;
+    pl->Pi = *pin;
+    pl->Po = *pout;
+    pl->rank = rank;
+    pl->E = e;
+    if (e) pl->extra.assign(extra_dims, extra_dims + e);
+    pl->esz = scalar_size * ncomp;
+    pl->ssz = scalar_size;
+    pl->ncomp = ncomp;
+    pl->msg_esz = pl->esz;
+    pl->R = R;
+    pl->aliased = (flags & 1) != 0;
+    if (keep_lo) {
+        /* the exchange of a keep plan is always a single group */
+        pl->keep = true;
+        pl->fill = fill;
+        pl->keep_lo.assign(keep_lo, keep_lo + n);
+        pl->keep_hi.assign(keep_hi, keep_hi + n);
+        if (fill == PA_FILL_ZERO) keep_fills(pl);
+    } else if (const char *ce = getenv("PENCILHIP_EXCHANGE_CHUNKS")) {
+        int c = atoi(ce);
+        if (c >= 1 && c <= 64) pl->chunks = c;
+    }
+    *out = pl;
+
+    Range axl_i[MAXND], axl_o[MAXND];
+    axes_for_rank(*pin, rank, axl_i);
+    axes_for_rank(*pout, rank, axl_o);
+    if (R < 0) {
+        /* local path (transpose_impl!(::Nothing), Transpositions.jl:214-271;
+         * aliased variant stages through recv_buf, :250-264) */
+        pl->P = 1;
+        pl->myk = 0;
+        pl->recv_total = self_block(pl, axl_i, 0);
+        return 0;
+    }
+
+    pl->P = (int)pin->topo.dims[R];
+    int64_t coords[MAXND];
+    cart_coords(pin->topo, rank, coords);
+    pl->myk = (int)coords[R];
+
+    Range self_region[MAXND];
+    int64_t isend = 0, irecv = 0;
+    for (int k = 0; k < pl->P; k++) {
+        int64_t pc[MAXND];
+        memcpy(pc, coords, sizeof(int64_t) * pin->topo.m);
+        pc[R] = k;
+        PeerBlockC blk;
+        blk.k = k;
+        blk.grank = cart_rank(pin->topo, pc);
+
+        Range axp_o[MAXND], axp_i[MAXND], sr[MAXND], rr[MAXND];
+        axes_for_coords(*pout, pc, axp_o);
+        axes_for_coords(*pin, pc, axp_i);
+        for (int d = 0; d < n; d++) {
+            range_intersect(axl_i[d], axp_o[d], &sr[d]); /* :383 */
+            range_intersect(axl_o[d], axp_i[d], &rr[d]); /* :388,:521 */
+        }
+        std::vector<Box> sb, rb;
+        sub_boxes(*pl, sr, &sb);
+        sub_boxes(*pl, rr, &rb);
+        for (auto &b : sb) blk.send_n += box_nelem(*pl, b);
+        for (auto &b : rb) blk.recv_n += box_nelem(*pl, b);
+        if (k == pl->myk) {
+            /* the self block (sr == rr) is never a message: fused, or staged
+             * at the recv tail once the remote blocks are laid out */
+            memcpy(self_region, sr, sizeof(Range) * n);
+        } else {
+            /* pack: column-major staging blocks in Pi memory order
+             * (:346-431); unpack: the same blocks scattered by the relative
+             * permutation (:527,:599-600) */
+            blk.send_off = isend;
+            blk.recv_off = irecv;
+            for (auto &b : sb) {
+                blk.pack.push_back(pack_sub(*pl, b, isend));
+                isend += blk.pack.back().n;
+            }
+            for (auto &b : rb) {
+                blk.unpack.push_back(unpack_sub(
+                    *pl, b, irecv, pl->keep ? nullptr : &blk.unpack_raw));
+                irecv += blk.unpack.back().n;
+            }
+            /* only an ordinary plan may chunk its exchange: its one
+             * sub-block is the whole block, and non-empty */
+            if (!pl->keep && !sb.empty()) {
+                blk.send_outer = outer_extent(*pl, sr);
+                blk.send_rowelems = blk.send_n / blk.send_outer;
+            }
+            if (!pl->keep && !rb.empty()) {
+                blk.has_unpack_raw = true;
+                blk.recv_outer = outer_extent(*pl, rr);
+                blk.recv_rowelems = blk.recv_n / blk.recv_outer;
+            }
+        }
+        pl->peers.push_back(blk);
+    }
+    pl->send_total = isend;
+    /* fused self path: direct window->window permuted copy (replaces
+     * :394-404 + :588-606; same values, half the HBM traffic).  Aliased
+     * (in-place) mode stages the self block at the END of the recv buffer
+     * like the reference, so every src read precedes any dst write. */
+    if (pl->aliased) pl->peers[pl->myk].recv_off = irecv;
+    pl->recv_total = self_block(pl, self_region, irecv);
+    return 0;
+}
+
+/* ---- reading the block tables --------------------------------------- */
+
+/* the sub-block list behind (which, k): 0 local, 1 pack of peer k, 2 unpack
+ * of peer k, 3 staged self pack, 4 staged self unpack; null for any other
+ * which or a peer the plan does not have */
+static const std::vector<SubC> *block_list(const pa_plan *p, int which, int k)
+{
+    if (which == 0) return &p->local;
+    if (which == 3) return &p->self_pack;
+    if (which == 4) return &p->self_unpack;
+    if (p->R < 0 || k < 0 || k >= (int)p->peers.size()) return nullptr;
+    if (which == 1) return &p->peers[k].pack;
+    if (which == 2) return &p->peers[k].unpack;
+    return nullptr;
+}
+
+/* Multi-field staging layout: a staging block at element offset o with c
+ * elements in the single-field plan holds field f of n at n*o + f*c; this is
+ * how far that moves the block's staging-side offset. */
+static inline int64_t many_shift(int n, int f, int64_t o, int64_t c)
+{
+    return (int64_t)(n - 1) * o + (int64_t)f * c;
+}
+
+static pa_status check_field(int n, int f)
+{
+    if (n < 1) return fail("n must be >= 1");
+    if (f < 0 || f >= n) return fail("field %d out of range", f);
+    return 0;
+}
+
+/* sub-block s of (which, k) for field f of n: its descriptor with the
+ * staging side (dst of a pack, src of an unpack) moved by many_shift */
+static pa_status field_desc(const pa_plan *p, int n, int f, int which, int k,
+                            int s, CopyDescH *out)
+{
+    if (pa_status st = check_field(n, f)) return st;
+    if (which < 0 || which > 4) return fail("bad which %d", which);
+    const std::vector<SubC> *l = block_list(p, which, k);
+    if (!l || s < 0 || s >= (int)l->size())
+        return fail("no sub-box %d (which %d, peer %d)", s, which, k);
+    const SubC &sb = (*l)[s];
+    *out = sb.d;
+    const int64_t sh = many_shift(n, f, sb.off, sb.n);
+    if (which == 1 || which == 3)
+        out->doff += sh;
+    else
+        out->soff += sh;
+    return 0;
+}
+
+/* the one descriptor of (which, k) on an ordinary plan, or the error naming
+ * what the plan lacks; `staged` words the missing self block for which 3/4 */
+static pa_status single_desc(const pa_plan *p, int n, int f, int which, int k,
+                             const char *const staged[2], CopyDescH *out)
+{
+    if (pa_status st = check_field(n, f)) return st;
+    const std::vector<SubC> *l = block_list(p, which, k);
+    if (l && !l->empty()) return field_desc(p, n, f, which, k, 0, out);
+    if (which == 0) return fail("no local copy in plan");
+    if (which == 3 || which == 4)
+        return fail("no staged self %s in plan", staged[which - 3]);
+    if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
+        return fail("no peer block %d", k);
+    if (which == 1) return fail("no pack for peer %d", k);
+    if (which == 2) return fail("no unpack for peer %d", k);
+    return fail("bad which %d", which);
+}
+
+static pa_status keep_has_no_single(void)
+{
+    return fail("a keep plan has one descriptor per sub-box: use "
+                "pa_plan_copydesc_sub");
+}
+
+static void copy_out(const CopyDescH &d, int64_t *nd, int64_t *dims,
+                     int64_t *sstr, int64_t *soff, int64_t *dstr,
+                     int64_t *doff)
+{
+    *nd = d.nd;
+    for (int i = 0; i < d.nd; i++) {
+        dims[i] = d.dims[i];
+        sstr[i] = d.sstr[i];
+        dstr[i] = d.dstr[i];
+    }
+    *soff = d.soff;
+    *doff = d.doff;
+}
+
+/* ---- what the two executes share ------------------------------------ */
+
+/* record timing event i on strm (pa_plan_enable_timing) */
+#define TM_REC(i, strm)                                                      \
+    do {                                                                     \
+        if (p->timing) {                                                     \
+            HIP_CHECK(hipEventRecord(p->tm[i], strm));                       \
+            p->tm_valid[i] = true;                                           \
+        }                                                                    \
+    } while (0)
+
+static pa_status timing_begin(pa_plan *p)
+{
+    if (!p->timing) return 0;
+    for (auto &e : p->tm)
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+    for (auto &v : p->tm_valid) v = false;
+    return 0;
+}
+
+/* does this rank send or receive any message? */
+static bool exchanging(const pa_plan *p)
+{
+    if (p->R >= 0 && p->P > 1)
+        for (auto &blk : p->peers)
+            if (blk.k != p->myk && (blk.send_n || blk.recv_n)) return true;
+    return false;
+}
+
+static pa_status ensure_comm_stream(pa_plan *p)
+{
+    if (p->comm_stream) return 0;
+    HIP_CHECK(hipStreamCreateWithFlags(&p->comm_stream,
+                                       hipStreamNonBlocking));
+    HIP_CHECK(hipEventCreateWithFlags(&p->ev_pack, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&p->ev_comm, hipEventDisableTiming));
+    return 0;
 }
 
 extern "C" {
@@ -2590,183 +2832,8 @@ pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
                               const int64_t *extra_dims, int rank, int flags,
                               pa_plan **out)
 {
-    /* assert_compatible (Transpositions.jl:182-199) */
-    if (pin->topo.m != pout->topo.m || pin->topo.dims != pout->topo.dims)
-        return fail("pencil topologies must be the same.");
-    if (pin->n != pout->n || pin->size_global != pout->size_global)
-        return fail("global data sizes must be the same between different "
-                    "pencil configurations.");
-    int ndiff = 0, R = -1;
-    for (int j = 0; j < pin->topo.m; j++)
-        if (pin->decomp[j] != pout->decomp[j]) {
-            ndiff++;
-            if (R < 0) R = j;
-        }
-    if (ndiff > 1)
-        return fail("pencil decompositions must differ in at most one "
-                    "dimension.");
-    if (rank < 0 || rank >= pin->topo.nranks) return fail("rank out of range");
-    if (pa_status cst = check_comp(scalar_size, ncomp)) return cst;
-    if (pin->n + e > MAXND)
-        return fail("too many dims: N+E must be <= %d", MAXND);
-
-    auto *pl = new pa_plan;
-    pl->Pi = *pin;
-    pl->Po = *pout;
-    pl->rank = rank;
-    pl->E = e;
-    if (e) pl->extra.assign(extra_dims, extra_dims + e);
-    pl->esz = scalar_size * ncomp;
-    pl->ssz = scalar_size;
-    pl->ncomp = ncomp;
-    pl->msg_esz = pl->esz;
-    pl->R = R;
-    pl->aliased = (flags & 1) != 0;
-    if (const char *ce = getenv("PENCILHIP_EXCHANGE_CHUNKS")) {
-        int c = atoi(ce);
-        if (c >= 1 && c <= 64) pl->chunks = c;
-    }
-
-    const int n = pin->n;
-    const int64_t pex = prod_extra(*pl);
-
-    if (R < 0) {
-        pl->P = 1;
-        pl->myk = 0;
-        /* local path (transpose_impl!(::Nothing), Transpositions.jl:214-271;
-         * aliased variant stages through recv_buf, :250-264) */
-        Range region[MAXND];
-        axes_for_rank(*pin, rank, region);
-        if (region_nelem(n, region) > 0) {
-            if (pl->aliased) {
-                staged_self_descs(pl, region, region, 0);
-                pl->recv_total = region_nelem(n, region) * pex;
-            } else {
-                int64_t dims[2 * MAXND], str[2 * MAXND], off;
-                int k;
-                window_desc(*pin, rank, pl->extra, region, dims, str, &off,
-                            &k);
-                pl->local = unpack_desc(*pl, region, dims, str, off);
-                pl->has_local = true;
-            }
-        }
-        *out = pl;
-        return 0;
-    }
-
-    pl->P = (int)pin->topo.dims[R];
-    int64_t coords[MAXND];
-    cart_coords(pin->topo, rank, coords);
-    pl->myk = (int)coords[R];
-
-    Range axl_i[MAXND], axl_o[MAXND];
-    axes_for_rank(*pin, rank, axl_i);
-    axes_for_rank(*pout, rank, axl_o);
-
-    int64_t isend = 0, irecv = 0;
-    for (int k = 0; k < pl->P; k++) {
-        int64_t pc[MAXND];
-        memcpy(pc, coords, sizeof(int64_t) * pin->topo.m);
-        pc[R] = k;
-        PeerBlockC blk;
-        blk.k = k;
-        blk.grank = cart_rank(pin->topo, pc);
-
-        Range axp_o[MAXND], axp_i[MAXND], sr[MAXND], rr[MAXND];
-        axes_for_coords(*pout, pc, axp_o);
-        axes_for_coords(*pin, pc, axp_i);
-        for (int d = 0; d < n; d++) {
-            range_intersect(axl_i[d], axp_o[d], &sr[d]); /* :383 */
-            range_intersect(axl_o[d], axp_i[d], &rr[d]); /* :388,:521 */
-        }
-        blk.send_n = region_nelem(n, sr) * pex;
-        blk.recv_n = region_nelem(n, rr) * pex;
-
-        if (k == pl->myk) {
-            blk.send_off = 0;
-            blk.recv_off = 0;
-            /* fused self path: direct window->window permuted copy
-             * (replaces :394-404 + :588-606; same values, half the HBM
-             * traffic).  Aliased (in-place) mode stages through the recv
-             * tail like the reference so every src read precedes any dst
-             * write. */
-            if (blk.send_n > 0) {
-                if (pl->aliased) {
-                    /* recv_off = length of remote recvs; filled below once
-                     * known: record block extents now, patch offset later */
-                    blk.recv_off = -1; /* placeholder, fixed after loop */
-                } else {
-                    int64_t dims[2 * MAXND], str[2 * MAXND], off;
-                    int kk;
-                    window_desc(*pin, rank, pl->extra, sr, dims, str, &off,
-                                &kk);
-                    pl->local = unpack_desc(*pl, rr, dims, str, off);
-                    pl->has_local = true;
-                }
-            }
-        } else {
-            blk.send_off = isend;
-            blk.recv_off = irecv;
-            if (blk.send_n > 0) {
-                int64_t dims[2 * MAXND], str[2 * MAXND], off;
-                int kk;
-                window_desc(*pin, rank, pl->extra, sr, dims, str, &off, &kk);
-                int64_t cstr[2 * MAXND], acc = 1;
-                for (int i = 0; i < kk; i++) {
-                    cstr[i] = acc;
-                    acc *= dims[i];
-                }
-                blk.pack = normalize_desc(kk, dims, str, off, cstr, isend);
-                blk.has_pack = true;
-                blk.send_outer = dims[kk - 1];
-                blk.send_rowelems = blk.send_n / (dims[kk - 1] ? dims[kk - 1] : 1);
-            }
-            if (blk.recv_n > 0) {
-                /* buffer dims: recv block extents gathered by Pi's
-                 * permutation (+ extras), column-major (:527,:599-600) */
-                int64_t bdims[2 * MAXND];
-                for (int i = 0; i < n; i++)
-                    bdims[i] = rr[pin->perm[i]].hi - rr[pin->perm[i]].lo;
-                for (int e2 = 0; e2 < e; e2++) bdims[n + e2] = pl->extra[e2];
-                int64_t bstr[2 * MAXND], acc = 1;
-                for (int i = 0; i < n + e; i++) {
-                    bstr[i] = acc;
-                    acc *= bdims[i];
-                }
-                blk.unpack = unpack_desc_raw_out(*pl, rr, bdims, bstr,
-                                                 irecv, &blk.unpack_raw);
-                blk.has_unpack = true;
-                blk.has_unpack_raw = true;
-                blk.recv_outer = bdims[(n + e) - 1];
-                blk.recv_rowelems =
-                    blk.recv_n / (blk.recv_outer ? blk.recv_outer : 1);
-            }
-            isend += blk.send_n;
-            irecv += blk.recv_n;
-        }
-        pl->peers.push_back(blk);
-    }
-    pl->send_total = isend;
-    pl->recv_total = irecv;
-    if (pl->aliased) {
-        /* self block at the END of the recv buffer (:394-404) */
-        PeerBlockC &self = pl->peers[pl->myk];
-        self.recv_off = irecv;
-        if (self.send_n > 0) {
-            Range pc_sr[MAXND], pc_rr[MAXND];
-            Range axp_o[MAXND], axp_i[MAXND];
-            axes_for_coords(*pout, coords, axp_o);
-            axes_for_coords(*pin, coords, axp_i);
-            for (int d = 0; d < n; d++) {
-                range_intersect(axl_i[d], axp_o[d], &pc_sr[d]);
-                range_intersect(axl_o[d], axp_i[d], &pc_rr[d]);
-            }
-            staged_self_descs(pl, pc_sr, pc_rr, irecv);
-            pl->recv_total = irecv + self.send_n;
-        }
-    }
-    *out = pl;
-    return 0;
+    return plan_build(pin, pout, scalar_size, ncomp, e, extra_dims, rank,
+                      flags, nullptr, nullptr, PA_FILL_NONE, out);
 }
 
 pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
@@ -2810,75 +2877,8 @@ pa_status pa_plan_create_keep(const pa_pencil *pin, const pa_pencil *pout,
                         ">= 0 and a + b <= %lld", d, (long long)keep_lo[d],
                         (long long)keep_hi[d],
                         (long long)pin->size_global[d]);
-    /* peers, their order and every validation are those of the ordinary
-     * plan; its block tables are then replaced by the sub-box tables */
-    pa_plan *pl = nullptr;
-    if (pa_status st = pa_plan_create_comp(pin, pout, scalar_size, ncomp, e,
-                                           extra_dims, rank, flags, &pl))
-        return st;
-    const int n = pin->n;
-    pl->keep = true;
-    pl->fill = fill;
-    pl->keep_lo.assign(keep_lo, keep_lo + n);
-    pl->keep_hi.assign(keep_hi, keep_hi + n);
-    pl->chunks = 1; /* the exchange of a keep plan is always a single group */
-    pl->has_local = pl->has_self = false;
-    pl->send_total = pl->recv_total = 0;
-    if (fill == PA_FILL_ZERO) keep_fills(pl);
-
-    if (pl->R < 0) {
-        Range region[MAXND];
-        axes_for_rank(*pin, rank, region);
-        pl->recv_total = keep_self_block(pl, region, 0);
-        *out = pl;
-        return 0;
-    }
-
-    int64_t coords[MAXND];
-    cart_coords(pin->topo, rank, coords);
-    Range axl_i[MAXND], axl_o[MAXND], self_region[MAXND];
-    axes_for_rank(*pin, rank, axl_i);
-    axes_for_rank(*pout, rank, axl_o);
-    int64_t isend = 0, irecv = 0;
-    for (auto &blk : pl->peers) {
-        int64_t pc[MAXND];
-        memcpy(pc, coords, sizeof(int64_t) * pin->topo.m);
-        pc[pl->R] = blk.k;
-        Range axp_o[MAXND], axp_i[MAXND], sr[MAXND], rr[MAXND];
-        axes_for_coords(*pout, pc, axp_o);
-        axes_for_coords(*pin, pc, axp_i);
-        for (int d = 0; d < n; d++) {
-            range_intersect(axl_i[d], axp_o[d], &sr[d]);
-            range_intersect(axl_o[d], axp_i[d], &rr[d]);
-        }
-        std::vector<Box> sb, rb;
-        sub_boxes(*pl, sr, &sb);
-        sub_boxes(*pl, rr, &rb);
-        blk.has_pack = blk.has_unpack = blk.has_unpack_raw = false;
-        blk.send_n = blk.recv_n = 0;
-        for (auto &b : sb) blk.send_n += box_nelem(*pl, b);
-        for (auto &b : rb) blk.recv_n += box_nelem(*pl, b);
-        blk.send_off = blk.recv_off = 0;
-        if (blk.k == pl->myk) {
-            memcpy(self_region, sr, sizeof(Range) * n);
-            continue;
-        }
-        blk.send_off = isend;
-        blk.recv_off = irecv;
-        for (auto &b : sb) {
-            blk.pack_subs.push_back(pack_sub(*pl, b, isend));
-            isend += blk.pack_subs.back().n;
-        }
-        for (auto &b : rb) {
-            blk.unpack_subs.push_back(unpack_sub(*pl, b, irecv));
-            irecv += blk.unpack_subs.back().n;
-        }
-    }
-    pl->send_total = isend;
-    if (pl->aliased) pl->peers[pl->myk].recv_off = irecv;
-    pl->recv_total = keep_self_block(pl, self_region, irecv);
-    *out = pl;
-    return 0;
+    return plan_build(pin, pout, scalar_size, ncomp, e, extra_dims, rank,
+                      flags, keep_lo, keep_hi, fill, out);
 }
 
 int pa_plan_keep(const pa_plan *p, int64_t *lo, int64_t *hi, int *fill)
@@ -2965,35 +2965,21 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
         return pa_transpose_execute_many(p, 1, srcs, dsts, stream_);
     }
 
-    if (p->timing) {
-        for (auto &e : p->tm)
-            if (!e) HIP_CHECK(hipEventCreate(&e));
-        for (auto &v : p->tm_valid) v = false;
-    }
-#define TM_REC(i, strm)                                                      \
-    do {                                                                     \
-        if (p->timing) {                                                     \
-            HIP_CHECK(hipEventRecord(p->tm[i], strm));                       \
-            p->tm_valid[i] = true;                                           \
-        }                                                                    \
-    } while (0)
+    if (pa_status st = timing_begin(p)) return st;
 
     /* 1. pack every remote block (Transpositions.jl:346-431); in aliased
      * mode also stage the self block into the recv tail before any dst
      * write (:394-404) */
     TM_REC(0, stream);
     for (auto &blk : p->peers)
-        if (blk.has_pack) {
-            pa_status st =
-                plan_launch(p, PA_WIRE_NARROW, blk.pack, src_parent,
-                            p->send_buf, stream);
-            if (st) return st;
-        }
-    if (p->has_self) {
-        pa_status st = plan_launch(p, PA_WIRE_NARROW, p->self_pack,
-                                   src_parent, p->recv_buf, stream);
-        if (st) return st;
-    }
+        for (auto &sb : blk.pack)
+            if (pa_status st = plan_launch(p, PA_WIRE_NARROW, sb.d,
+                                           src_parent, p->send_buf, stream))
+                return st;
+    for (auto &sb : p->self_pack)
+        if (pa_status st = plan_launch(p, PA_WIRE_NARROW, sb.d, src_parent,
+                                       p->recv_buf, stream))
+            return st;
     TM_REC(1, stream);
 
     /* 2. exchange: grouped ncclSend/ncclRecv over xGMI on a dedicated comm
@@ -3003,24 +2989,12 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
      * caller's stream CONCURRENTLY with the exchange — the engine's
      * equivalent of the reference's unpack-local-while-recvs-fly overlap
      * (Transpositions.jl:510-517). */
-    bool exchanging = false;
-    if (p->R >= 0 && p->P > 1) {
-        for (auto &blk : p->peers)
-            if (blk.k != p->myk && (blk.send_n || blk.recv_n))
-                exchanging = true;
-    }
-    const int C = (exchanging && p->chunks > 1) ? p->chunks : 1;
-    if (exchanging) {
+    const bool xchg = exchanging(p);
+    const int C = (xchg && p->chunks > 1) ? p->chunks : 1;
+    if (xchg) {
         if (!p->comm)
             return fail("subgroup exchange requires pa_plan_set_comm");
-        if (!p->comm_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&p->comm_stream,
-                                               hipStreamNonBlocking));
-            HIP_CHECK(hipEventCreateWithFlags(&p->ev_pack,
-                                              hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&p->ev_comm,
-                                              hipEventDisableTiming));
-        }
+        if (pa_status st = ensure_comm_stream(p)) return st;
         while ((int)p->ev_chunks.size() < C) {
             hipEvent_t e;
             HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -3072,33 +3046,28 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
 
     /* 3. fused local/self copy — on the caller's stream, overlapping the
      * exchange (aliased mode: unpack the staged self block instead) */
-    if (p->has_local) {
-        pa_status st =
-            plan_launch(p, PA_WIRE_ROUND, p->local, src_parent, dst_parent,
-                        stream);
-        if (st) return st;
-    }
-    if (p->has_self) {
-        pa_status st = plan_launch(p, PA_WIRE_WIDEN, p->self_unpack,
-                                   p->recv_buf, dst_parent, stream);
-        if (st) return st;
-    }
+    for (auto &sb : p->local)
+        if (pa_status st = plan_launch(p, PA_WIRE_ROUND, sb.d, src_parent,
+                                       dst_parent, stream))
+            return st;
+    for (auto &sb : p->self_unpack)
+        if (pa_status st = plan_launch(p, PA_WIRE_WIDEN, sb.d, p->recv_buf,
+                                       dst_parent, stream))
+            return st;
     TM_REC(2, stream);
 
     /* 4. unpack received blocks (:489-536).  C == 1: all after the single
      * exchange completes.  C > 1: chunk c unpacks as soon as its group
      * lands, overlapping chunks c+1.. in flight. */
     if (C <= 1) {
-        if (exchanging)
-            HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
+        if (xchg) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
         TM_REC(5, stream);
         for (auto &blk : p->peers)
-            if (blk.has_unpack) {
-                pa_status st =
-                    plan_launch(p, PA_WIRE_WIDEN, blk.unpack, p->recv_buf,
-                                dst_parent, stream);
-                if (st) return st;
-            }
+            for (auto &sb : blk.unpack)
+                if (pa_status st = plan_launch(p, PA_WIRE_WIDEN, sb.d,
+                                               p->recv_buf, dst_parent,
+                                               stream))
+                    return st;
         TM_REC(6, stream);
     } else {
         for (int c = 0; c < C; c++) {
@@ -3118,8 +3087,6 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
         }
         TM_REC(6, stream);
     }
-#undef TM_REC
-
     return 0;
 }
 
@@ -3175,8 +3142,8 @@ pa_status pa_plan_block_info(const pa_plan *p, int k, int64_t out[8])
     out[3] = b.recv_off;
     out[4] = b.send_n;
     out[5] = b.recv_n;
-    out[6] = b.has_pack || !b.pack_subs.empty();
-    out[7] = b.has_unpack || !b.unpack_subs.empty();
+    out[6] = !b.pack.empty();
+    out[7] = !b.unpack.empty();
     return 0;
 }
 
@@ -3184,47 +3151,17 @@ pa_status pa_plan_copydesc(const pa_plan *p, int which, int k, int64_t *nd,
                            int64_t *dims, int64_t *sstr, int64_t *soff,
                            int64_t *dstr, int64_t *doff)
 {
-    const CopyDescH *d = nullptr;
-    if (p->keep)
-        return fail("a keep plan has one descriptor per sub-box: use "
-                    "pa_plan_copydesc_sub");
-    if (which == 0) {
-        if (!p->has_local) return fail("no local copy in plan");
-        d = &p->local;
-    } else if (which == 3) {
-        if (!p->has_self) return fail("no staged self pack in plan");
-        d = &p->self_pack;
-    } else if (which == 4) {
-        if (!p->has_self) return fail("no staged self unpack in plan");
-        d = &p->self_unpack;
-    } else if (which == 5) {
+    static const char *const staged[2] = {"pack", "unpack"};
+    if (p->keep) return keep_has_no_single();
+    CopyDescH d;
+    if (which == 5) { /* raw (un-normalized) unpack: nd = n+E <= MAXND */
         if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
             return fail("no peer block %d", k);
         if (!p->peers[k].has_unpack_raw) return fail("no raw unpack");
-        d = &p->peers[k].unpack_raw;
-        /* raw: may exceed normalized nd cap assumptions of callers; nd <= 2*MAXND
-         * but CopyDescH holds MAXND — enforced at plan build (n+E <= MAXND). */
-    } else {
-        if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
-            return fail("no peer block %d", k);
-        const PeerBlockC &b = p->peers[k];
-        if (which == 1) {
-            if (!b.has_pack) return fail("no pack for peer %d", k);
-            d = &b.pack;
-        } else if (which == 2) {
-            if (!b.has_unpack) return fail("no unpack for peer %d", k);
-            d = &b.unpack;
-        } else
-            return fail("bad which %d", which);
-    }
-    *nd = d->nd;
-    for (int i = 0; i < d->nd; i++) {
-        dims[i] = d->dims[i];
-        sstr[i] = d->sstr[i];
-        dstr[i] = d->dstr[i];
-    }
-    *soff = d->soff;
-    *doff = d->doff;
+        d = p->peers[k].unpack_raw;
+    } else if (pa_status st = single_desc(p, 1, 0, which, k, staged, &d))
+        return st;
+    copy_out(d, nd, dims, sstr, soff, dstr, doff);
     return 0;
 }
 
@@ -3351,94 +3288,6 @@ enum {
     STAGE_LOCAL = PA_STAGE_LOCAL,
     STAGE_UNPACK = PA_STAGE_UNPACK
 };
-
-static inline int64_t many_shift(int n, int f, int64_t o, int64_t c)
-{
-    return (int64_t)(n - 1) * o + (int64_t)f * c;
-}
-
-/* the descriptor of field f: the single-field one with its staging-side
- * offset moved; `which` as in pa_plan_copydesc (0..4) */
-static pa_status many_desc(const pa_plan *p, int n, int f, int which, int k,
-                           CopyDescH *out)
-{
-    if (n < 1) return fail("n must be >= 1");
-    if (f < 0 || f >= n) return fail("field %d out of range", f);
-    if (which == 0) {
-        if (!p->has_local) return fail("no local copy in plan");
-        *out = p->local;
-        return 0;
-    }
-    if (which == 3 || which == 4) {
-        if (!p->has_self) return fail("no staged self block in plan");
-        const int64_t sh =
-            many_shift(n, f, p->self_pack.doff, p->self_pack.total);
-        *out = which == 3 ? p->self_pack : p->self_unpack;
-        if (which == 3)
-            out->doff += sh;
-        else
-            out->soff += sh;
-        return 0;
-    }
-    if (p->R < 0 || k < 0 || k >= (int)p->peers.size())
-        return fail("no peer block %d", k);
-    const PeerBlockC &b = p->peers[k];
-    if (which == 1) {
-        if (!b.has_pack) return fail("no pack for peer %d", k);
-        *out = b.pack;
-        out->doff += many_shift(n, f, b.send_off, b.send_n);
-        return 0;
-    }
-    if (which == 2) {
-        if (!b.has_unpack) return fail("no unpack for peer %d", k);
-        *out = b.unpack;
-        out->soff += many_shift(n, f, b.recv_off, b.recv_n);
-        return 0;
-    }
-    return fail("bad which %d", which);
-}
-
-/* keep plans: how many sub-boxes `which` (of peer k) has, and sub-box s of
- * field f with the multi-field rule applied to ITS staging block */
-static const std::vector<SubC> *sub_list(const pa_plan *p, int which, int k)
-{
-    if (which == 3) return &p->self_pack_subs;
-    if (which == 4) return &p->self_unpack_subs;
-    if (p->R < 0 || k < 0 || k >= (int)p->peers.size()) return nullptr;
-    if (which == 1) return &p->peers[k].pack_subs;
-    if (which == 2) return &p->peers[k].unpack_subs;
-    return nullptr;
-}
-
-static int sub_count(const pa_plan *p, int which, int k)
-{
-    if (which == 0) return (int)p->local_subs.size();
-    const std::vector<SubC> *l = sub_list(p, which, k);
-    return l ? (int)l->size() : 0;
-}
-
-static pa_status sub_desc(const pa_plan *p, int n, int f, int which, int k,
-                          int s, CopyDescH *out)
-{
-    if (!p->keep) return fail("not a keep plan");
-    if (n < 1) return fail("n must be >= 1");
-    if (f < 0 || f >= n) return fail("field %d out of range", f);
-    if (which < 0 || which > 4) return fail("bad which %d", which);
-    if (s < 0 || s >= sub_count(p, which, k))
-        return fail("no sub-box %d (which %d, peer %d)", s, which, k);
-    if (which == 0) {
-        *out = p->local_subs[s];
-        return 0;
-    }
-    const SubC &sb = (*sub_list(p, which, k))[s];
-    *out = sb.d;
-    const int64_t sh = many_shift(n, f, sb.off, sb.n);
-    if (which == 1 || which == 3)
-        out->doff += sh;
-    else
-        out->soff += sh;
-    return 0;
-}
 
 struct StageItem {
     KernelSel k;
@@ -3586,19 +3435,13 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         t->launches.push_back(l);
         return 0;
     };
+    /* every sub-block of `which` (of peer k) for field f */
     auto add = [&](int f, int which, int k, const void *src,
                    void *dst) -> pa_status {
-        CopyDescH d;
-        if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
-        return add_desc(d, which, src, dst);
-    };
-    /* keep plans: every sub-box of `which` (of peer k) for field f */
-    auto add_subs = [&](int f, int which, int k, const void *src,
-                        void *dst) -> pa_status {
-        const int ns = sub_count(p, which, k);
-        for (int s = 0; s < ns; s++) {
+        const std::vector<SubC> *l = block_list(p, which, k);
+        for (int s = 0; l && s < (int)l->size(); s++) {
             CopyDescH d;
-            if (pa_status st = sub_desc(p, n, f, which, k, s, &d)) return st;
+            if (pa_status st = field_desc(p, n, f, which, k, s, &d)) return st;
             if (pa_status st = add_desc(d, which, src, dst)) return st;
         }
         return 0;
@@ -3630,58 +3473,29 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         return 0;
     };
 
-    if (p->keep) {
-        for (int f = 0; f < n; f++) {
-            const void *src = srcs ? srcs[f] : nullptr;
-            void *dst = dsts ? dsts[f] : nullptr;
-            if (stage == STAGE_PACK) {
-                for (auto &b : p->peers)
-                    if (pa_status st = add_subs(f, 1, b.k, src,
-                                                (void *)send_buf))
-                        return st;
-                if (pa_status st = add_subs(f, 3, 0, src, recv_buf))
-                    return st;
-            } else if (stage == STAGE_LOCAL) {
-                if (pa_status st = add_subs(f, 0, 0, src, dst)) return st;
-                if (pa_status st = add_subs(f, 4, 0, recv_buf, dst))
-                    return st;
-            } else {
-                for (auto &b : p->peers)
-                    if (pa_status st = add_subs(f, 2, b.k, recv_buf, dst))
-                        return st;
-            }
-        }
-        /* the fill entries of every field, after the copies of the stage */
-        if (stage == STAGE_LOCAL)
-            for (int f = 0; f < n; f++)
-                for (auto &fd : p->fills)
-                    if (pa_status st = add_fill(fd, dsts ? dsts[f] : nullptr))
-                        return st;
-        return 0;
-    }
-
     for (int f = 0; f < n; f++) {
         const void *src = srcs ? srcs[f] : nullptr;
         void *dst = dsts ? dsts[f] : nullptr;
         if (stage == STAGE_PACK) {
             for (auto &b : p->peers)
-                if (b.has_pack)
-                    if (pa_status st = add(f, 1, b.k, src, (void *)send_buf))
-                        return st;
-            if (p->has_self)
-                if (pa_status st = add(f, 3, 0, src, recv_buf)) return st;
+                if (pa_status st = add(f, 1, b.k, src, (void *)send_buf))
+                    return st;
+            if (pa_status st = add(f, 3, 0, src, recv_buf)) return st;
         } else if (stage == STAGE_LOCAL) {
-            if (p->has_local)
-                if (pa_status st = add(f, 0, 0, src, dst)) return st;
-            if (p->has_self)
-                if (pa_status st = add(f, 4, 0, recv_buf, dst)) return st;
+            if (pa_status st = add(f, 0, 0, src, dst)) return st;
+            if (pa_status st = add(f, 4, 0, recv_buf, dst)) return st;
         } else {
             for (auto &b : p->peers)
-                if (b.has_unpack)
-                    if (pa_status st = add(f, 2, b.k, recv_buf, dst))
-                        return st;
+                if (pa_status st = add(f, 2, b.k, recv_buf, dst)) return st;
         }
     }
+    /* the fill entries of every field (keep plans), after the copies of the
+     * stage */
+    if (stage == STAGE_LOCAL)
+        for (int f = 0; f < n; f++)
+            for (auto &fd : p->fills)
+                if (pa_status st = add_fill(fd, dsts ? dsts[f] : nullptr))
+                    return st;
     return 0;
 }
 
@@ -3932,19 +3746,11 @@ pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
                                 int64_t *doff)
 {
     if (!p) return fail("null plan");
-    if (p->keep)
-        return fail("a keep plan has one descriptor per sub-box: use "
-                    "pa_plan_copydesc_sub");
+    static const char *const staged[2] = {"block", "block"};
+    if (p->keep) return keep_has_no_single();
     CopyDescH d;
-    if (pa_status st = many_desc(p, n, f, which, k, &d)) return st;
-    *nd = d.nd;
-    for (int i = 0; i < d.nd; i++) {
-        dims[i] = d.dims[i];
-        sstr[i] = d.sstr[i];
-        dstr[i] = d.dstr[i];
-    }
-    *soff = d.soff;
-    *doff = d.doff;
+    if (pa_status st = single_desc(p, n, f, which, k, staged, &d)) return st;
+    copy_out(d, nd, dims, sstr, soff, dstr, doff);
     return 0;
 }
 
@@ -3995,7 +3801,8 @@ int64_t pa_plan_stage_table_builds(const pa_plan *p)
 int pa_plan_nsub(const pa_plan *p, int which, int k)
 {
     if (!p || !p->keep || which < 0 || which > 4) return 0;
-    return sub_count(p, which, k);
+    const std::vector<SubC> *l = block_list(p, which, k);
+    return l ? (int)l->size() : 0;
 }
 
 pa_status pa_plan_copydesc_sub(const pa_plan *p, int n, int f, int which,
@@ -4004,16 +3811,10 @@ pa_status pa_plan_copydesc_sub(const pa_plan *p, int n, int f, int which,
                                int64_t *doff)
 {
     if (!p) return fail("null plan");
+    if (!p->keep) return fail("not a keep plan");
     CopyDescH d;
-    if (pa_status st = sub_desc(p, n, f, which, k, s, &d)) return st;
-    *nd = d.nd;
-    for (int i = 0; i < d.nd; i++) {
-        dims[i] = d.dims[i];
-        sstr[i] = d.sstr[i];
-        dstr[i] = d.dstr[i];
-    }
-    *soff = d.soff;
-    *doff = d.doff;
+    if (pa_status st = field_desc(p, n, f, which, k, s, &d)) return st;
+    copy_out(d, nd, dims, sstr, soff, dstr, doff);
     return 0;
 }
 
@@ -4106,26 +3907,10 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
     hipStream_t stream = (hipStream_t)stream_;
     if (pa_status st = many_check(p, n, STAGE_LOCAL, srcs, dsts)) return st;
 
-    bool exchanging = false;
-    if (p->R >= 0 && p->P > 1)
-        for (auto &blk : p->peers)
-            if (blk.k != p->myk && (blk.send_n || blk.recv_n))
-                exchanging = true;
-    if (exchanging && !p->comm)
+    const bool xchg = exchanging(p);
+    if (xchg && !p->comm)
         return fail("subgroup exchange requires pa_plan_set_comm");
-
-    if (p->timing) {
-        for (auto &e : p->tm)
-            if (!e) HIP_CHECK(hipEventCreate(&e));
-        for (auto &v : p->tm_valid) v = false;
-    }
-#define TM_REC(i, strm)                                                      \
-    do {                                                                     \
-        if (p->timing) {                                                     \
-            HIP_CHECK(hipEventRecord(p->tm[i], strm));                       \
-            p->tm_valid[i] = true;                                           \
-        }                                                                    \
-    } while (0)
+    if (pa_status st = timing_begin(p)) return st;
 
     /* 1. every pack and staged self pack of every field, before any write
      * of a destination */
@@ -4136,15 +3921,8 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
 
     /* 2. one grouped exchange, one message per peer carrying all n fields,
      * on the comm stream, event-ordered like pa_transpose_execute */
-    if (exchanging) {
-        if (!p->comm_stream) {
-            HIP_CHECK(hipStreamCreateWithFlags(&p->comm_stream,
-                                               hipStreamNonBlocking));
-            HIP_CHECK(hipEventCreateWithFlags(&p->ev_pack,
-                                              hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&p->ev_comm,
-                                              hipEventDisableTiming));
-        }
+    if (xchg) {
+        if (pa_status st = ensure_comm_stream(p)) return st;
         HIP_CHECK(hipEventRecord(p->ev_pack, stream));
         HIP_CHECK(hipStreamWaitEvent(p->comm_stream, p->ev_pack, 0));
         TM_REC(3, p->comm_stream);
@@ -4175,7 +3953,7 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
     TM_REC(2, stream);
 
     /* 4. unpack every received block of every field */
-    if (exchanging) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
+    if (xchg) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
     TM_REC(5, stream);
     if (pa_status st = run_stage(p, n, STAGE_UNPACK, nullptr, dsts, stream))
         return st;

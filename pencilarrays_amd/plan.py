@@ -90,6 +90,14 @@ def normalize_desc(d: CopyDesc) -> CopyDesc:
 # --------------------------------------------------------------------------
 
 
+def _single(subs, keep):
+    """Read-only single-descriptor view of a sub-block list: the one
+    descriptor of an ordinary plan; None on a keep plan or when absent."""
+    if keep is not None or not subs:
+        return None
+    return getattr(subs[0], "desc", subs[0])
+
+
 @dataclass
 class PeerBlock:
     peer_k: int                 # coordinate along R == subgroup rank
@@ -100,12 +108,15 @@ class PeerBlock:
     recv_nelem: int
     send_offset: int            # element offset into send staging buffer
     recv_offset: int            # element offset into recv staging buffer
-    pack: Optional[CopyDesc]    # src parent -> send buffer (None if empty/self)
-    unpack: Optional[CopyDesc]  # recv buffer -> dst parent (None if empty/self)
-    # keep plans (build_plan(keep=...)): one staging block per non-empty
-    # sub-box of the block; ``pack``/``unpack`` stay None
+    keep: Optional[Tuple[Tuple[int, int], ...]] = None  # the plan's keep set
+    # one staging block per non-empty sub-box of the block: src parent ->
+    # send buffer, recv buffer -> dst parent (empty for the self block).  An
+    # ordinary plan, whose keep set is everything, has at most one each.
     pack_subs: List["SubBlock"] = field(default_factory=list)
     unpack_subs: List["SubBlock"] = field(default_factory=list)
+
+    pack = property(lambda self: _single(self.pack_subs, self.keep))
+    unpack = property(lambda self: _single(self.unpack_subs, self.keep))
 
 
 @dataclass
@@ -118,26 +129,28 @@ class TransposePlan:
     nproc_sub: int                  # subgroup size P (1 if local path)
     my_k: int                       # my coordinate along R
     peers: List[PeerBlock] = field(default_factory=list)
-    local: Optional[CopyDesc] = None  # fused self/local permuted copy
     send_nelem_total: int = 0
     recv_nelem_total: int = 0       # staging incl. self tail when aliased
     aliased: bool = False
-    # aliased (in-place) mode: the self block stages through the recv-buffer
-    # tail instead of the fused direct copy (the reference's aliasing path:
-    # Transpositions.jl:250-264 for the local case, :394-404 placement for
-    # the distributed case), so every read of src completes before any write
-    # of dst.
-    self_pack: Optional[CopyDesc] = None    # src -> recv_buf tail
-    self_unpack: Optional[CopyDesc] = None  # recv_buf tail -> dst
     # truncated transposes (keep plans): the keep set as (a, b) per logical
-    # dim, the fill mode, and the sub-box tables that replace the single
-    # descriptors above (which stay None)
+    # dim and the fill mode; every count and offset is then in KEPT elements
     keep: Optional[Tuple[Tuple[int, int], ...]] = None
     fill: int = 0
+    # The self block, one entry per non-empty sub-box (at most one on an
+    # ordinary plan): fused src-window -> dst-window copies, or in aliased
+    # (in-place) mode staged through the recv-buffer tail (the reference's
+    # aliasing path: Transpositions.jl:250-264 for the local case, :394-404
+    # placement for the distributed case), so every read of src completes
+    # before any write of dst.
     local_subs: List[CopyDesc] = field(default_factory=list)
     self_pack_subs: List["SubBlock"] = field(default_factory=list)
     self_unpack_subs: List["SubBlock"] = field(default_factory=list)
     fills: List["FillDesc"] = field(default_factory=list)
+
+    local = property(lambda self: _single(self.local_subs, self.keep))
+    self_pack = property(lambda self: _single(self.self_pack_subs, self.keep))
+    self_unpack = property(
+        lambda self: _single(self.self_unpack_subs, self.keep))
 
     @property
     def subgroup_global_ranks(self) -> List[int]:
@@ -161,165 +174,148 @@ def _window_desc_src(p: Pencil, rank: int, region: Region,
     parent of pencil ``p``, axes in p's memory order (+ extra axes)."""
     local = p.to_local(rank, region, memory_order=True)  # mem-order local ranges
     _, pst = _parent_strides(p, rank, extra_dims)
-    n = p.ndims
     dims = tuple(hi - lo for lo, hi in local) + tuple(extra_dims)
-    strides = pst  # one per mem axis then extra axes
     offset = sum(lo * pst[i] for i, (lo, _) in enumerate(local))
-    return dims, strides, offset
+    return dims, pst, offset  # one stride per mem axis, then the extra axes
 
 
 def build_plan(Pi: Pencil, Po: Pencil, rank: int,
                extra_dims: Tuple[int, ...] = (),
                aliased: bool = False, keep=None,
                fill="zero") -> TransposePlan:
-    """``keep`` (a sequence of ``(a, b)`` per logical dim, ``None`` entries
-    meaning full) builds a truncated transpose: see :func:`build_keep_plan`.
-    Without it the tables are the ordinary ones and ``fill`` is ignored."""
-    if keep is not None:
-        return build_keep_plan(Pi, Po, rank, extra_dims, aliased, keep, fill)
+    """The block tables of ``rank``'s transpose ``Pi -> Po``.
+
+    ``keep`` (a sequence of ``(a, b)`` per logical dim, ``None`` entries
+    meaning full) builds a truncated transpose: every block is intersected
+    with the keep set, every count and offset is in KEPT elements, each block
+    holds one descriptor per non-empty sub-box, and ``fills`` lists the
+    destination windows outside the keep set when ``fill`` is zero.  Without
+    it the keep set is everything: a block is its own single sub-box,
+    readable as ``pack`` / ``unpack`` / ``local`` / ``self_pack`` /
+    ``self_unpack``, and ``fill`` is ignored."""
     extra_dims = tuple(int(e) for e in extra_dims)
     R = Pi.transpose_dim(Po)  # validates compatibility
-    n = Pi.ndims
-    E = len(extra_dims)
+    n, E = Pi.ndims, len(extra_dims)
+    size = Pi.size_global
+    pex = math.prod(extra_dims or (1,))
+    fcode = FILL_NONE
+    if keep is not None:
+        keep = normalize_keep(size, keep)
+        fcode = fill_code(fill)
 
     # Relative permutation Po-mem-axis -> Pi-mem-axis (Transpositions.jl:506):
     # dest memory axis i' holds logical dim permo[i'], which sits at source
     # memory axis inv(permi)[permo[i']].
-    permi = perm_apply(Pi.perm, tuple(range(n)))  # == Pi.perm
-    permo = Po.perm
-    q_rel = perm_relative(permo, permi)           # len n
+    q_rel = perm_relative(Po.perm, Pi.perm)
     q_full = tuple(q_rel) + tuple(n + i for i in range(E))
     inv_q = perm_inv(q_full)
+    _, pst_o = _parent_strides(Po, rank, extra_dims)
 
     plan = TransposePlan(
-        rank=rank, Pi=Pi, Po=Po, extra_dims=extra_dims,
-        r_dim=R, nproc_sub=1 if R is None else Pi.topology.dims[R],
-        my_k=0, aliased=aliased,
-    )
+        rank=rank, Pi=Pi, Po=Po, extra_dims=extra_dims, r_dim=R,
+        nproc_sub=1 if R is None else Pi.topology.dims[R], my_k=0,
+        aliased=aliased, keep=keep, fill=fcode)
 
-    mem_o, pst_o = _parent_strides(Po, rank, extra_dims)
+    def boxes(region: Region) -> List[Region]:
+        """The sub-boxes of a block.  An ordinary plan keeps everything, so
+        the region itself, gated as ordinary plans always were: a block of a
+        subgroup on its element count, extras included, and the
+        same-decomposition block on its geometry alone."""
+        if keep is not None:
+            return sub_boxes(region, keep, size)
+        nelem = region_nelem(region) * (1 if R is None else pex)
+        return [region] if nelem > 0 else []
 
-    def unpack_like(buf_dims: Tuple[int, ...], dst_local_mem: Region,
-                    src_strides: Tuple[int, ...], src_offset: int) -> CopyDesc:
+    def to_dst(buf_dims, box: Region, src_strides, src_offset) -> CopyDesc:
         """CopyDesc moving a block laid out on ``src`` (axes = Pi-mem order +
-        extras, strides given) into the Po parent window starting at
-        ``dst_local_mem`` (Po-mem-order local ranges)."""
-        # buffer axis j feeds dest mem axis inv_q-of... dst axis i' reads
-        # buffer axis q_full[i']; so dstride[j] = pst_o[inv_q[j]] and the
-        # dest offset uses the window start of axis inv_q[j].
-        starts = tuple(lo for lo, _ in dst_local_mem) + (0,) * E
+        extras, strides given) into the Po parent window of ``box``: buffer
+        axis j feeds dest mem axis inv_q[j]."""
+        starts = tuple(lo for lo, _ in
+                       Po.to_local(rank, box, memory_order=True)) + (0,) * E
         dstrides = tuple(pst_o[inv_q[j]] for j in range(n + E))
         doffset = sum(starts[i] * pst_o[i] for i in range(n + E))
-        return normalize_desc(CopyDesc(
-            dims=buf_dims, sstrides=src_strides, soffset=src_offset,
-            dstrides=dstrides, doffset=doffset,
-        ))
+        return normalize_desc(CopyDesc(buf_dims, src_strides, src_offset,
+                                       dstrides, doffset))
 
-    def staged_self(region_in: Region, region_out: Region, recv_off: int):
-        """Self block via the recv-buffer tail (in-place/aliased mode)."""
-        sdims, sst, soff = _window_desc_src(Pi, rank, region_in, extra_dims)
-        plan.self_pack = normalize_desc(CopyDesc(
-            dims=sdims, sstrides=sst, soffset=soff,
-            dstrides=_colmajor_strides(sdims), doffset=recv_off,
-        ))
-        bdims = (perm_apply(Pi.perm, region_lengths(region_out))
-                 + tuple(extra_dims))
-        dst_local = Po.to_local(rank, region_out, memory_order=True)
-        plan.self_unpack = unpack_like(
-            bdims, dst_local, _colmajor_strides(bdims), recv_off)
+    def pack_sub(box: Region, off: int) -> SubBlock:
+        sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
+        return SubBlock(box, off, region_nelem(box) * pex, normalize_desc(
+            CopyDesc(sdims, sst, soff, _colmajor_strides(sdims), off)))
+
+    def unpack_sub(box: Region, off: int) -> SubBlock:
+        # the buffer holds the box in Pi memory order of ITS window
+        bdims = perm_apply(Pi.perm, region_lengths(box)) + extra_dims
+        return SubBlock(box, off, region_nelem(box) * pex,
+                        to_dst(bdims, box, _colmajor_strides(bdims), off))
+
+    def self_block(region: Region, off: int) -> int:
+        """The self block: the fused direct src-window -> dst-window permuted
+        copy (replaces the reference's copy to the recv_buf tail :394-404
+        followed by copy_permuted! — same values, half the HBM traffic).  In
+        aliased (in-place) mode that copy would read windows the unpacks
+        overwrite, so the block is staged at ``off`` like the reference.
+        Returns the end offset."""
+        for box in boxes(region):
+            if aliased:
+                ps = pack_sub(box, off)
+                plan.self_pack_subs.append(ps)
+                plan.self_unpack_subs.append(unpack_sub(box, off))
+                off += ps.nelem
+            else:
+                sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
+                plan.local_subs.append(to_dst(sdims, box, sst, soff))
+        return off
+
+    if fcode == FILL_ZERO:
+        axes_o = Po.axes_for_rank(rank)
+        for box in fill_regions(keep, size):
+            box = region_intersect(box, axes_o)
+            if region_nelem(box) == 0 or pex == 0:
+                continue
+            loc = Po.to_local(rank, box, memory_order=True)
+            dims = tuple(hi - lo for lo, hi in loc) + extra_dims
+            off = sum(lo * pst_o[i] for i, (lo, _) in enumerate(loc))
+            plan.fills.append(_fill_desc(dims, pst_o, off))
 
     if R is None:
         # Same decomposition: plain copy or local permutation
         # (transpose_impl!(::Nothing), Transpositions.jl:214-271; in-place
         # variant stages through recv_buf, :250-264).
-        region = Pi.axes_for_rank(rank)
-        if region_nelem(region) > 0:
-            if aliased:
-                staged_self(region, region, 0)
-                plan.recv_nelem_total = (region_nelem(region)
-                                         * math.prod(extra_dims or (1,)))
-            else:
-                sdims, sst, soff = _window_desc_src(Pi, rank, region,
-                                                    extra_dims)
-                dst_local = Po.to_local(rank, region, memory_order=True)
-                plan.local = unpack_like(sdims, dst_local, sst, soff)
+        plan.recv_nelem_total = self_block(Pi.axes_for_rank(rank), 0)
         return plan
 
     topo = Pi.topology
     coords = topo.cart_coords(rank)
     plan.my_k = coords[R]
-    P = topo.dims[R]
-
     axes_local_i = Pi.axes_for_rank(rank)
     axes_local_o = Po.axes_for_rank(rank)
-
-    isend = 0
-    irecv = 0
-    # length of data exchanged with myself (Transpositions.jl:303-306)
-    self_region = region_intersect(axes_local_i, axes_local_o)
-    length_self = region_nelem(self_region) * math.prod(extra_dims or (1,))
-    length_recv_remote = (Po.length_local(rank) * math.prod(extra_dims or (1,))
-                          - length_self)
-
-    for k in range(P):
-        peer_coords = list(coords)
-        peer_coords[R] = k
-        peer_coords = tuple(peer_coords)
-        grank = topo.cart_rank(peer_coords)
-
-        srange = region_intersect(axes_local_i, Po.axes_for_coords(peer_coords))
-        rrange = region_intersect(axes_local_o, Pi.axes_for_coords(peer_coords))
-        ns = region_nelem(srange) * math.prod(extra_dims or (1,))
-        nr = region_nelem(rrange) * math.prod(extra_dims or (1,))
-
+    isend = irecv = 0
+    for k in range(topo.dims[R]):
+        pc = list(coords)
+        pc[R] = k
+        pc = tuple(pc)
+        srange = region_intersect(axes_local_i, Po.axes_for_coords(pc))
+        rrange = region_intersect(axes_local_o, Pi.axes_for_coords(pc))
+        sboxes, rboxes = boxes(srange), boxes(rrange)
         blk = PeerBlock(
-            peer_k=k, global_rank=grank,
-            send_region=srange, recv_region=rrange,
-            send_nelem=ns, recv_nelem=nr,
-            send_offset=0, recv_offset=0, pack=None, unpack=None,
-        )
-
-        if k == plan.my_k:
-            # Fused self path: direct src-window -> dst-window permuted copy
-            # (replaces the reference's copy to the recv_buf tail :394-404
-            # followed by copy_permuted! — same values, half the HBM traffic).
-            # In aliased (in-place) mode the direct copy would read windows
-            # the unpacks overwrite, so the self block stages through the
-            # recv tail exactly like the reference.
-            assert nr == length_self and ns == length_self
-            blk.recv_offset = length_recv_remote  # kept for reference parity
-            if ns > 0:
-                if aliased:
-                    staged_self(srange, rrange, length_recv_remote)
-                else:
-                    sdims, sst, soff = _window_desc_src(Pi, rank, srange,
-                                                        extra_dims)
-                    dst_local = Po.to_local(rank, rrange, memory_order=True)
-                    plan.local = unpack_like(sdims, dst_local, sst, soff)
-        else:
-            blk.send_offset = isend
-            blk.recv_offset = irecv
-            if ns > 0:
-                sdims, sst, soff = _window_desc_src(Pi, rank, srange, extra_dims)
-                blk.pack = normalize_desc(CopyDesc(
-                    dims=sdims, sstrides=sst, soffset=soff,
-                    dstrides=_colmajor_strides(sdims), doffset=isend,
-                ))
-            if nr > 0:
-                # buffer holds the block in Pi memory order of ITS window
-                bdims = (perm_apply(Pi.perm, region_lengths(rrange))
-                         + tuple(extra_dims))
-                dst_local = Po.to_local(rank, rrange, memory_order=True)
-                blk.unpack = unpack_like(
-                    bdims, dst_local, _colmajor_strides(bdims), irecv)
-            isend += ns
-            irecv += nr
-
+            peer_k=k, global_rank=topo.cart_rank(pc), send_region=srange,
+            recv_region=rrange,
+            send_nelem=sum(region_nelem(b) for b in sboxes) * pex,
+            recv_nelem=sum(region_nelem(b) for b in rboxes) * pex,
+            send_offset=0, recv_offset=0, keep=keep)
+        if k != plan.my_k:
+            blk.send_offset, blk.recv_offset = isend, irecv
+            for box in sboxes:
+                blk.pack_subs.append(pack_sub(box, isend))
+                isend += blk.pack_subs[-1].nelem
+            for box in rboxes:
+                blk.unpack_subs.append(unpack_sub(box, irecv))
+                irecv += blk.unpack_subs[-1].nelem
         plan.peers.append(blk)
-
     plan.send_nelem_total = isend
-    assert irecv == length_recv_remote
-    plan.recv_nelem_total = irecv + (length_self if aliased else 0)
+    self_blk = plan.peers[plan.my_k]
+    self_blk.recv_offset = irecv  # the self block sits at the recv tail
+    plan.recv_nelem_total = self_block(self_blk.send_region, irecv)
     return plan
 
 
@@ -484,178 +480,8 @@ def _fill_desc(dims, strides, offset) -> FillDesc:
 def build_keep_plan(Pi: Pencil, Po: Pencil, rank: int,
                     extra_dims: Tuple[int, ...], aliased: bool, keep,
                     fill="zero") -> TransposePlan:
-    """The plan of a truncated transpose.  Blocks, peers and their order are
-    those of :func:`build_plan`; every count and offset is in KEPT elements;
-    the single descriptors (``pack``, ``unpack``, ``local``, ``self_pack``,
-    ``self_unpack``) are None and the ``*_subs`` tables hold one descriptor
-    per non-empty sub-box.  ``fills`` lists the destination windows outside
-    the keep set when ``fill`` is zero."""
-    extra_dims = tuple(int(e) for e in extra_dims)
-    R = Pi.transpose_dim(Po)
-    n, E = Pi.ndims, len(extra_dims)
-    size = Pi.size_global
-    keep = normalize_keep(size, keep)
-    fcode = fill_code(fill)
-    pex = math.prod(extra_dims or (1,))
-
-    q_rel = perm_relative(Po.perm, Pi.perm)
-    q_full = tuple(q_rel) + tuple(n + i for i in range(E))
-    inv_q = perm_inv(q_full)
-    _, pst_o = _parent_strides(Po, rank, extra_dims)
-
-    plan = TransposePlan(
-        rank=rank, Pi=Pi, Po=Po, extra_dims=extra_dims, r_dim=R,
-        nproc_sub=1 if R is None else Pi.topology.dims[R], my_k=0,
-        aliased=aliased, keep=keep, fill=fcode)
-
-    def to_dst(buf_dims, box: Region, src_strides, src_offset) -> CopyDesc:
-        starts = tuple(lo for lo, _ in
-                       Po.to_local(rank, box, memory_order=True)) + (0,) * E
-        dstrides = tuple(pst_o[inv_q[j]] for j in range(n + E))
-        doffset = sum(starts[i] * pst_o[i] for i in range(n + E))
-        return normalize_desc(CopyDesc(buf_dims, src_strides, src_offset,
-                                       dstrides, doffset))
-
-    def pack_sub(box: Region, off: int) -> SubBlock:
-        sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
-        return SubBlock(box, off, region_nelem(box) * pex, normalize_desc(
-            CopyDesc(sdims, sst, soff, _colmajor_strides(sdims), off)))
-
-    def unpack_sub(box: Region, off: int) -> SubBlock:
-        bdims = perm_apply(Pi.perm, region_lengths(box)) + extra_dims
-        return SubBlock(box, off, region_nelem(box) * pex,
-                        to_dst(bdims, box, _colmajor_strides(bdims), off))
-
-    def local_sub(box: Region) -> CopyDesc:
-        sdims, sst, soff = _window_desc_src(Pi, rank, box, extra_dims)
-        return to_dst(sdims, box, sst, soff)
-
-    def self_block(region: Region, off: int) -> int:
-        """Sub-boxes of the self block: fused, or staged at ``off``."""
-        for box in sub_boxes(region, keep, size):
-            if aliased:
-                ps = pack_sub(box, off)
-                plan.self_pack_subs.append(ps)
-                plan.self_unpack_subs.append(unpack_sub(box, off))
-                off += ps.nelem
-            else:
-                plan.local_subs.append(local_sub(box))
-        return off
-
-    if fcode == FILL_ZERO:
-        axes_o = Po.axes_for_rank(rank)
-        for box in fill_regions(keep, size):
-            box = region_intersect(box, axes_o)
-            if region_nelem(box) == 0 or pex == 0:
-                continue
-            loc = Po.to_local(rank, box, memory_order=True)
-            dims = tuple(hi - lo for lo, hi in loc) + extra_dims
-            off = sum(lo * pst_o[i] for i, (lo, _) in enumerate(loc))
-            plan.fills.append(_fill_desc(dims, pst_o, off))
-
-    if R is None:
-        plan.recv_nelem_total = self_block(Pi.axes_for_rank(rank), 0)
-        return plan
-
-    topo = Pi.topology
-    coords = topo.cart_coords(rank)
-    plan.my_k = coords[R]
-    axes_local_i = Pi.axes_for_rank(rank)
-    axes_local_o = Po.axes_for_rank(rank)
-    isend = irecv = 0
-    for k in range(topo.dims[R]):
-        pc = list(coords)
-        pc[R] = k
-        pc = tuple(pc)
-        srange = region_intersect(axes_local_i, Po.axes_for_coords(pc))
-        rrange = region_intersect(axes_local_o, Pi.axes_for_coords(pc))
-        blk = PeerBlock(
-            peer_k=k, global_rank=topo.cart_rank(pc), send_region=srange,
-            recv_region=rrange, send_nelem=0, recv_nelem=0, send_offset=0,
-            recv_offset=0, pack=None, unpack=None)
-        sboxes = sub_boxes(srange, keep, size)
-        rboxes = sub_boxes(rrange, keep, size)
-        blk.send_nelem = sum(region_nelem(b) for b in sboxes) * pex
-        blk.recv_nelem = sum(region_nelem(b) for b in rboxes) * pex
-        if k != plan.my_k:
-            blk.send_offset, blk.recv_offset = isend, irecv
-            for box in sboxes:
-                blk.pack_subs.append(pack_sub(box, isend))
-                isend += blk.pack_subs[-1].nelem
-            for box in rboxes:
-                blk.unpack_subs.append(unpack_sub(box, irecv))
-                irecv += blk.unpack_subs[-1].nelem
-        plan.peers.append(blk)
-    plan.send_nelem_total = isend
-    self_blk = plan.peers[plan.my_k]
-    self_blk.recv_offset = irecv  # the self block sits at the recv tail
-    plan.recv_nelem_total = self_block(self_blk.send_region, irecv)
-    return plan
-
-
-def nsub(plan: TransposePlan, which: int, k: int = 0) -> int:
-    """Sub-boxes behind ``which`` (as in :func:`copydesc_many`) of a keep
-    plan; peer ``k`` for packs and unpacks."""
-    if plan.keep is None:
-        raise ValueError("not a keep plan")
-    if which == 0:
-        return len(plan.local_subs)
-    if which in (3, 4):
-        return len(plan.self_pack_subs)
-    if plan.r_dim is None or not 0 <= k < len(plan.peers):
-        return 0
-    if which == 1:
-        return len(plan.peers[k].pack_subs)
-    if which == 2:
-        return len(plan.peers[k].unpack_subs)
-    raise ValueError(f"bad which {which}")
-
-
-def copydesc_sub(plan: TransposePlan, n: int, f: int, which: int, k: int,
-                 s: int) -> Optional[CopyDesc]:
-    """Sub-box ``s`` of field ``f`` of ``n`` on a keep plan, ``which`` as in
-    :func:`copydesc_many`.  The multi-field rule holds per sub-box: field
-    ``f`` sits at ``n*o_s + f*c_s``."""
-    _check_many(n, f)
-    if not 0 <= s < nsub(plan, which, k):
-        return None
-    if which == 0:
-        return plan.local_subs[s]
-    if which == 1:
-        sb = plan.peers[k].pack_subs[s]
-    elif which == 2:
-        sb = plan.peers[k].unpack_subs[s]
-    elif which == 3:
-        sb = plan.self_pack_subs[s]
-    else:
-        sb = plan.self_unpack_subs[s]
-    d, sh = sb.desc, many_shift(n, f, sb.offset, sb.nelem)
-    if which in (1, 3):
-        return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
-                        d.doffset + sh)
-    return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides, d.doffset)
-
-
-def stage_descs(plan: TransposePlan, n: int, f: int, stage: int):
-    """``(which, desc)`` for every copy that ``stage`` (0 pack, 1 local,
-    2 unpack) runs for field ``f`` of ``n`` on a keep plan, in launch order."""
-    out = []
-    if stage == 0:
-        for blk in plan.peers:
-            for s in range(len(blk.pack_subs)):
-                out.append((1, copydesc_sub(plan, n, f, 1, blk.peer_k, s)))
-        for s in range(len(plan.self_pack_subs)):
-            out.append((3, copydesc_sub(plan, n, f, 3, 0, s)))
-    elif stage == 1:
-        for d in plan.local_subs:
-            out.append((0, d))
-        for s in range(len(plan.self_unpack_subs)):
-            out.append((4, copydesc_sub(plan, n, f, 4, 0, s)))
-    else:
-        for blk in plan.peers:
-            for s in range(len(blk.unpack_subs)):
-                out.append((2, copydesc_sub(plan, n, f, 2, blk.peer_k, s)))
-    return out
+    """The plan of a truncated transpose: ``build_plan(..., keep=keep)``."""
+    return build_plan(Pi, Po, rank, extra_dims, aliased, keep, fill)
 
 
 # --------------------------------------------------------------------------
@@ -684,43 +510,81 @@ def _check_many(n: int, f: int = 0):
         raise ValueError(f"field {f} out of range for n = {n}")
 
 
-def copydesc_many(plan: TransposePlan, n: int, f: int, which: int,
-                  k: int = 0) -> Optional[CopyDesc]:
-    """The descriptor of field ``f`` of ``n``; ``which`` as in
-    ``pa_plan_copydesc``: 0 local, 1 pack of peer k, 2 unpack of peer k,
-    3 staged self pack, 4 staged self unpack.  None where the plan has no
-    such descriptor."""
-    _check_many(n, f)
+def _subs(plan: TransposePlan, which: int, k: int):
+    """The sub-block list behind ``which``: 0 local, 1 pack of peer k,
+    2 unpack of peer k, 3 staged self pack, 4 staged self unpack.  None for
+    a peer the plan does not have."""
     if which == 0:
-        return plan.local
+        return plan.local_subs
     if which in (3, 4):
-        if plan.self_pack is None:
-            return None
-        sh = many_shift(n, f, plan.self_pack.doffset, plan.self_pack.nelem)
-        d = plan.self_pack if which == 3 else plan.self_unpack
-        if which == 3:
-            return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
-                            d.doffset + sh)
-        return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides,
-                        d.doffset)
+        return plan.self_pack_subs if which == 3 else plan.self_unpack_subs
     if plan.r_dim is None or not 0 <= k < len(plan.peers):
         return None
-    blk = plan.peers[k]
     if which == 1:
-        d = blk.pack
-        if d is None:
-            return None
-        sh = many_shift(n, f, blk.send_offset, blk.send_nelem)
+        return plan.peers[k].pack_subs
+    if which == 2:
+        return plan.peers[k].unpack_subs
+    raise ValueError(f"bad which {which}")
+
+
+def _field_desc(plan: TransposePlan, n: int, f: int, which: int, k: int,
+                s: int) -> CopyDesc:
+    """Sub-block ``s`` of ``(which, k)`` for field ``f`` of ``n``: its
+    descriptor with the staging side (dst of a pack, src of an unpack) moved
+    by :func:`many_shift`; field ``f`` of a block sits at ``n*o_s + f*c_s``."""
+    sb = _subs(plan, which, k)[s]
+    if which == 0:
+        return sb
+    d, sh = sb.desc, many_shift(n, f, sb.offset, sb.nelem)
+    if which in (1, 3):
         return CopyDesc(d.dims, d.sstrides, d.soffset, d.dstrides,
                         d.doffset + sh)
-    if which == 2:
-        d = blk.unpack
-        if d is None:
-            return None
-        sh = many_shift(n, f, blk.recv_offset, blk.recv_nelem)
-        return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides,
-                        d.doffset)
-    raise ValueError(f"bad which {which}")
+    return CopyDesc(d.dims, d.sstrides, d.soffset + sh, d.dstrides, d.doffset)
+
+
+def copydesc_many(plan: TransposePlan, n: int, f: int, which: int,
+                  k: int = 0) -> Optional[CopyDesc]:
+    """The descriptor of field ``f`` of ``n`` on an ordinary plan; ``which``
+    as in ``pa_plan_copydesc``: 0 local, 1 pack of peer k, 2 unpack of peer k,
+    3 staged self pack, 4 staged self unpack.  None where the plan has no
+    such descriptor, and on a keep plan (see :func:`copydesc_sub`)."""
+    _check_many(n, f)
+    if not _subs(plan, which, k) or plan.keep is not None:
+        return None
+    return _field_desc(plan, n, f, which, k, 0)
+
+
+def nsub(plan: TransposePlan, which: int, k: int = 0) -> int:
+    """Sub-boxes behind ``which`` (as in :func:`copydesc_many`) of a keep
+    plan; peer ``k`` for packs and unpacks."""
+    if plan.keep is None:
+        raise ValueError("not a keep plan")
+    subs = _subs(plan, which, k)
+    return 0 if subs is None else len(subs)
+
+
+def copydesc_sub(plan: TransposePlan, n: int, f: int, which: int, k: int,
+                 s: int) -> Optional[CopyDesc]:
+    """Sub-box ``s`` of field ``f`` of ``n`` on a keep plan, ``which`` as in
+    :func:`copydesc_many`; None past the last sub-box."""
+    _check_many(n, f)
+    if not 0 <= s < nsub(plan, which, k):
+        return None
+    return _field_desc(plan, n, f, which, k, s)
+
+
+def stage_descs(plan: TransposePlan, n: int, f: int, stage: int):
+    """``(which, desc)`` for every copy that ``stage`` (0 pack, 1 local,
+    2 unpack) runs for field ``f`` of ``n``, in launch order, on any plan."""
+    if stage == 0:
+        blocks = [(1, blk.peer_k) for blk in plan.peers] + [(3, 0)]
+    elif stage == 1:
+        blocks = [(0, 0), (4, 0)]
+    else:
+        blocks = [(2, blk.peer_k) for blk in plan.peers]
+    return [(which, _field_desc(plan, n, f, which, k, s))
+            for which, k in blocks
+            for s in range(len(_subs(plan, which, k)))]
 
 
 def buffer_nelem_many(plan: TransposePlan, n: int) -> Tuple[int, int]:

@@ -20,7 +20,7 @@ Execution backends:
 
 from __future__ import annotations
 
-from typing import Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -28,7 +28,7 @@ from .array import PencilArray
 from .copyexec import apply_copy, apply_copy_conv, apply_fill
 from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
-                   copydesc_many, peer_message, stage_descs)
+                   peer_message, stage_descs)
 from .plan import fourier_keep  # noqa: F401  (the keep-set helper, re-exported)
 from .wire import narrow, resolve_wire, widen
 
@@ -36,12 +36,10 @@ MPI_TAG = 42  # Transpositions.jl:469
 
 
 def _wire(buf: np.ndarray):
-    """A staging-buffer slice as a torch tensor for isend/irecv; opaque
-    (void) elements travel as their bytes."""
+    """A staging-buffer slice as a torch tensor for isend/irecv: elements of
+    any kind (opaque, wire scalars) travel as their bytes."""
     import torch
-    if buf.dtype.kind == "V":
-        buf = buf.view(np.uint8)
-    return torch.from_numpy(buf)
+    return torch.from_numpy(buf.view(np.uint8))
 
 
 def _wire_pair(dest: PencilArray, src: PencilArray, wire_dtype):
@@ -64,10 +62,51 @@ def _check_keep_wire(keep, wire_dtype):
             "transpose moves the stored type")
 
 
-def _wire_convs(pair):
-    """(narrow, widen, round) of a wire pair as elementwise functions."""
-    return (lambda x: narrow(x, pair), lambda w: widen(w, pair),
-            lambda x: widen(narrow(x, pair), pair))
+class _Codec(NamedTuple):
+    """The two things in which the host mirror of a reduced-precision wire
+    differs from the plain one: how an array and the staging buffers are
+    typed, and the copy that runs a descriptor."""
+    view: Callable        # PencilArray -> the flat array descriptors index
+    carrier: Optional[np.dtype]  # staging dtype; None = that of the view
+    scale: int            # staging scalars per element
+    copy: Callable        # (which, desc, src, dst): run one descriptor
+
+
+def _codec(src: PencilArray, pair) -> _Codec:
+    if pair is None:
+        # plain elements: one opaque item per element (vector-valued ones
+        # included), so the element-unit descriptors apply unchanged
+        return _Codec(lambda a: a.element_view(), None, 1,
+                      lambda which, d, s, t: apply_copy(d, s, t))
+    # wire: packs narrow, unpacks widen, the local copy rounds
+    nc = src.ncomp * pair.comps  # stored scalars per element
+    conv = {0: lambda x: widen(narrow(x, pair), pair),
+            1: lambda x: narrow(x, pair), 2: lambda w: widen(w, pair)}
+    conv[3], conv[4] = conv[1], conv[2]  # the staged self block likewise
+    return _Codec(lambda a: a.data.view(pair.stored), pair.carrier, nc,
+                  lambda which, d, s, t: apply_copy_conv(d, s, t, nc,
+                                                         conv[which]))
+
+
+def _dist_for(plan: TransposePlan, use_dist: bool):
+    """torch.distributed for the exchange of ``plan``: one process per rank,
+    so its rank and world must be the topology's (a mismatch would silently
+    address the wrong peers)."""
+    if not use_dist:
+        raise RuntimeError(
+            "distributed transpose requires torch.distributed to be "
+            "initialised (or use run_transpose_sim for in-process tests)")
+    import torch.distributed as dist
+    topo = plan.Pi.topology
+    if dist.get_world_size() != topo.nranks:
+        raise RuntimeError(
+            f"torch.distributed world size {dist.get_world_size()} != "
+            f"topology nranks {topo.nranks}")
+    if dist.get_rank() != plan.rank:
+        raise RuntimeError(
+            f"torch.distributed rank {dist.get_rank()} != topology "
+            f"rank {plan.rank}")
+    return dist
 
 
 def _arrays_alias(a, b) -> bool:
@@ -144,204 +183,53 @@ class Transposition:
     # ------------------------------------------------------------------
 
     def _execute_numpy(self, use_dist: bool):
-        if self.wire is not None:
-            return self._execute_numpy_wire(use_dist)
-        if self.plan.keep is not None:
-            return self._execute_numpy_keep(use_dist)
+        """Every stage of any plan through ``stage_descs``: one copy per
+        sub-block, one message per peer of the elements that move, the zero
+        fill of a keep plan next to the local copy."""
         plan = self.plan
-        # vector-valued elements: one opaque B-byte item per element, so the
-        # element-unit descriptors apply unchanged
-        src_flat = self.src.element_view()
-        dst_flat = self.dest.element_view()
-
-        if plan.r_dim is None or plan.nproc_sub == 1:
-            if plan.local is not None:
-                apply_copy(plan.local, src_flat, dst_flat)
-            elif plan.self_pack is not None:
-                # in-place: stage through recv buffer (Transpositions.jl:250-264)
-                recv_buf = np.empty(plan.recv_nelem_total, dtype=src_flat.dtype)
-                apply_copy(plan.self_pack, src_flat, recv_buf)
-                apply_copy(plan.self_unpack, recv_buf, dst_flat)
-            return
-
-        if not use_dist:
-            raise RuntimeError(
-                "distributed transpose requires torch.distributed to be "
-                "initialised (or use run_transpose_sim for in-process tests)")
-
-        import torch
-        import torch.distributed as dist
-
-        # one process per rank: dist rank/world must match the topology
-        # (a mismatch would silently address the wrong peers)
-        topo = plan.Pi.topology
-        if dist.get_world_size() != topo.nranks:
-            raise RuntimeError(
-                f"torch.distributed world size {dist.get_world_size()} != "
-                f"topology nranks {topo.nranks}")
-        if dist.get_rank() != plan.rank:
-            raise RuntimeError(
-                f"torch.distributed rank {dist.get_rank()} != topology "
-                f"rank {plan.rank}")
-
-        send_buf = np.empty(plan.send_nelem_total, dtype=src_flat.dtype)
-        recv_buf = np.empty(plan.recv_nelem_total, dtype=src_flat.dtype)
+        codec = _codec(self.src, self.wire)
+        src, dst = codec.view(self.src), codec.view(self.dest)
+        dt, sc = codec.carrier or src.dtype, codec.scale
+        send_buf = np.empty(plan.send_nelem_total * sc, dtype=dt)
+        recv_buf = np.empty(plan.recv_nelem_total * sc, dtype=dt)
 
         # 1. pack all remote blocks (Transpositions.jl:346-431); in aliased
         # mode also stage the self block into the recv tail BEFORE any write
         # of dst (:394-404)
-        for blk in plan.peers:
-            if blk.pack is not None:
-                apply_copy(blk.pack, src_flat, send_buf)
-        if plan.self_pack is not None:
-            apply_copy(plan.self_pack, src_flat, recv_buf)
+        for which, d in stage_descs(plan, 1, 0, 0):
+            codec.copy(which, d, src, send_buf if which == 1 else recv_buf)
 
-        # 2. exchange: per-peer nonblocking send/recv (:463-479)
+        # 2. exchange: per-peer nonblocking send/recv (:463-479); a peer with
+        # nothing kept is absent from it.  An ordinary plan asks for the
+        # process group whenever its subgroup has peers.
         reqs = []
-        for blk in plan.peers:
-            if blk.peer_k == plan.my_k:
-                continue
-            if blk.recv_nelem > 0:
-                rt = _wire(
-                    recv_buf[blk.recv_offset:blk.recv_offset + blk.recv_nelem])
-                reqs.append(dist.irecv(rt, src=blk.global_rank, tag=MPI_TAG))
-            if blk.send_nelem > 0:
-                st = _wire(
-                    send_buf[blk.send_offset:blk.send_offset + blk.send_nelem])
-                reqs.append(dist.isend(st, dst=blk.global_rank, tag=MPI_TAG))
+        msgs = [blk for blk in plan.peers if blk.peer_k != plan.my_k
+                and (blk.send_nelem or blk.recv_nelem)]
+        if msgs or (plan.keep is None and plan.nproc_sub > 1):
+            dist = _dist_for(plan, use_dist)
+            for blk in msgs:
+                if blk.recv_nelem > 0:
+                    rt = _wire(recv_buf[blk.recv_offset * sc:
+                                        (blk.recv_offset + blk.recv_nelem) * sc])
+                    reqs.append(dist.irecv(rt, src=blk.global_rank,
+                                           tag=MPI_TAG))
+                if blk.send_nelem > 0:
+                    st = _wire(send_buf[blk.send_offset * sc:
+                                        (blk.send_offset + blk.send_nelem) * sc])
+                    reqs.append(dist.isend(st, dst=blk.global_rank,
+                                           tag=MPI_TAG))
 
         # 3. fused local (self) block overlaps the exchange (:394-404 + :530)
-        if plan.local is not None:
-            apply_copy(plan.local, src_flat, dst_flat)
-        elif plan.self_unpack is not None:
-            apply_copy(plan.self_unpack, recv_buf, dst_flat)
-
+        for which, d in stage_descs(plan, 1, 0, 1):
+            codec.copy(which, d, src if which == 0 else recv_buf, dst)
+        for fd in plan.fills:
+            apply_fill(fd, dst)
         for r in reqs:
             r.wait()
 
         # 4. unpack received blocks (:489-536)
-        for blk in plan.peers:
-            if blk.unpack is not None:
-                apply_copy(blk.unpack, recv_buf, dst_flat)
-
-    def _execute_numpy_keep(self, use_dist: bool):
-        """The same stages on a keep plan: one copy per sub-box, messages of
-        the kept elements only, and the zero fill next to the local copy."""
-        plan = self.plan
-        src_flat = self.src.element_view()
-        dst_flat = self.dest.element_view()
-        send_buf = np.empty(plan.send_nelem_total, dtype=src_flat.dtype)
-        recv_buf = np.empty(plan.recv_nelem_total, dtype=src_flat.dtype)
-
-        # every pack (and staged self pack) before any write of dst
-        for which, d in stage_descs(plan, 1, 0, 0):
-            apply_copy(d, src_flat, send_buf if which == 1 else recv_buf)
-
-        reqs = []
-        msgs = [blk for blk in plan.peers if blk.peer_k != plan.my_k
-                and (blk.send_nelem or blk.recv_nelem)]
-        if msgs:
-            if not use_dist:
-                raise RuntimeError(
-                    "distributed transpose requires torch.distributed to be "
-                    "initialised (or use run_transpose_sim for in-process "
-                    "tests)")
-            import torch.distributed as dist
-            topo = plan.Pi.topology
-            if dist.get_world_size() != topo.nranks:
-                raise RuntimeError(
-                    f"torch.distributed world size {dist.get_world_size()} "
-                    f"!= topology nranks {topo.nranks}")
-            if dist.get_rank() != plan.rank:
-                raise RuntimeError(
-                    f"torch.distributed rank {dist.get_rank()} != topology "
-                    f"rank {plan.rank}")
-            # a peer with nothing kept is absent from the exchange
-            for blk in msgs:
-                if blk.recv_nelem > 0:
-                    rt = _wire(recv_buf[
-                        blk.recv_offset:blk.recv_offset + blk.recv_nelem])
-                    reqs.append(dist.irecv(rt, src=blk.global_rank,
-                                           tag=MPI_TAG))
-                if blk.send_nelem > 0:
-                    st = _wire(send_buf[
-                        blk.send_offset:blk.send_offset + blk.send_nelem])
-                    reqs.append(dist.isend(st, dst=blk.global_rank,
-                                           tag=MPI_TAG))
-
-        for which, d in stage_descs(plan, 1, 0, 1):
-            apply_copy(d, src_flat if which == 0 else recv_buf, dst_flat)
-        for fd in plan.fills:
-            apply_fill(fd, dst_flat)
-        for r in reqs:
-            r.wait()
-        for _, d in stage_descs(plan, 1, 0, 2):
-            apply_copy(d, recv_buf, dst_flat)
-
-    def _execute_numpy_wire(self, use_dist: bool):
-        """The same stages with a reduced-precision wire: staging buffers of
-        the wire type, packs narrow, unpacks widen, the local copy rounds."""
-        plan, pair = self.plan, self.wire
-        nc = self.src.ncomp * pair.comps  # stored scalars per element
-        src = self.src.data.view(pair.stored)
-        dst = self.dest.data.view(pair.stored)
-        nar, wid, rnd = _wire_convs(pair)
-        send_buf = np.empty(plan.send_nelem_total * nc, dtype=pair.carrier)
-        recv_buf = np.empty(plan.recv_nelem_total * nc, dtype=pair.carrier)
-        exchanging = plan.r_dim is not None and plan.nproc_sub > 1
-
-        for blk in plan.peers:
-            if blk.pack is not None:
-                apply_copy_conv(blk.pack, src, send_buf, nc, nar)
-        if plan.self_pack is not None:
-            apply_copy_conv(plan.self_pack, src, recv_buf, nc, nar)
-
-        reqs = []
-        if exchanging:
-            if not use_dist:
-                raise RuntimeError(
-                    "distributed transpose requires torch.distributed to be "
-                    "initialised (or use run_transpose_sim for in-process "
-                    "tests)")
-            import torch
-            import torch.distributed as dist
-            topo = plan.Pi.topology
-            if dist.get_world_size() != topo.nranks:
-                raise RuntimeError(
-                    f"torch.distributed world size {dist.get_world_size()} "
-                    f"!= topology nranks {topo.nranks}")
-            if dist.get_rank() != plan.rank:
-                raise RuntimeError(
-                    f"torch.distributed rank {dist.get_rank()} != topology "
-                    f"rank {plan.rank}")
-            for blk in plan.peers:
-                if blk.peer_k == plan.my_k:
-                    continue
-                # the wire-typed slices travel as their bytes
-                if blk.recv_nelem > 0:
-                    rt = torch.from_numpy(recv_buf[
-                        blk.recv_offset * nc:
-                        (blk.recv_offset + blk.recv_nelem) * nc
-                    ].view(np.uint8))
-                    reqs.append(dist.irecv(rt, src=blk.global_rank,
-                                           tag=MPI_TAG))
-                if blk.send_nelem > 0:
-                    st = torch.from_numpy(send_buf[
-                        blk.send_offset * nc:
-                        (blk.send_offset + blk.send_nelem) * nc
-                    ].view(np.uint8))
-                    reqs.append(dist.isend(st, dst=blk.global_rank,
-                                           tag=MPI_TAG))
-
-        if plan.local is not None:
-            apply_copy_conv(plan.local, src, dst, nc, rnd)
-        elif plan.self_unpack is not None:
-            apply_copy_conv(plan.self_unpack, recv_buf, dst, nc, wid)
-        for r in reqs:
-            r.wait()
-        for blk in plan.peers:
-            if blk.unpack is not None:
-                apply_copy_conv(blk.unpack, recv_buf, dst, nc, wid)
+        for which, d in stage_descs(plan, 1, 0, 2):
+            codec.copy(which, d, recv_buf, dst)
 
     # ------------------------------------------------------------------
     # GPU execution — native HIP engine only.
@@ -530,169 +418,38 @@ def run_transpose_sim(dests: Sequence[PencilArray],
                       srcs: Sequence[PencilArray],
                       staging_out=None, wire_dtype=None, keep=None,
                       fill="zero") -> None:
-    """``staging_out``, if a dict, receives the final ``send``/``recv``
-    staging buffers per rank.  ``wire_dtype``: a reduced-precision wire (see
-    :class:`Transposition`); the staging buffers then hold wire scalars.
-    ``keep`` / ``fill``: a truncated transpose (see :class:`Transposition`);
-    the staging buffers then hold the kept elements only."""
-    _check_keep_wire(keep, wire_dtype)
-    if wire_dtype is not None or keep is not None:
-        return run_transpose_sim_many([[d] for d in dests],
-                                      [[s] for s in srcs], staging_out,
-                                      wire_dtype=wire_dtype, keep=keep,
-                                      fill=fill)
-    nranks = len(srcs)
-    plans = [build_plan(s.pencil, d.pencil, r, s.extra_dims,
-                        aliased=_arrays_alias(s.data, d.data))
-             for r, (d, s) in enumerate(zip(dests, srcs))]
-    for d, s in zip(dests, srcs):
-        if d.elem_dims != s.elem_dims:
-            raise ValueError(
-                f"incompatible element dimensions of PencilArrays: "
-                f"{s.elem_dims} != {d.elem_dims}")
-    sflat = [s.element_view() for s in srcs]
-    dflat = [d.element_view() for d in dests]
-
-    send_bufs = [np.empty(p.send_nelem_total, dtype=sflat[r].dtype)
-                 for r, p in enumerate(plans)]
-    recv_bufs = [np.empty(p.recv_nelem_total, dtype=sflat[r].dtype)
-                 for r, p in enumerate(plans)]
-
-    # pack on every rank (incl. staged self blocks, before any dst write)
-    for r, p in enumerate(plans):
-        for blk in p.peers:
-            if blk.pack is not None:
-                apply_copy(blk.pack, sflat[r], send_bufs[r])
-        if p.self_pack is not None:
-            apply_copy(p.self_pack, sflat[r], recv_bufs[r])
-    for r, p in enumerate(plans):
-        if p.local is not None:
-            apply_copy(p.local, sflat[r], dflat[r])
-        elif p.self_unpack is not None:
-            apply_copy(p.self_unpack, recv_bufs[r], dflat[r])
-
-    # exchange: copy each send block into the receiver's recv buffer
-    for r, p in enumerate(plans):
-        for blk in p.peers:
-            if blk.peer_k == p.my_k or blk.send_nelem == 0:
-                continue
-            # The matching recv block on the peer: the peer's PeerBlock whose
-            # peer coordinate equals MY coordinate along R.
-            q = plans[blk.global_rank]
-            rblk = q.peers[p.my_k]
-            assert rblk.global_rank == r and rblk.recv_nelem == blk.send_nelem, \
-                (r, blk, rblk)
-            recv_bufs[blk.global_rank][
-                rblk.recv_offset:rblk.recv_offset + rblk.recv_nelem] = \
-                send_bufs[r][blk.send_offset:blk.send_offset + blk.send_nelem]
-
-    # unpack on every rank
-    for r, p in enumerate(plans):
-        for blk in p.peers:
-            if blk.unpack is not None:
-                apply_copy(blk.unpack, recv_bufs[r], dflat[r])
-    if staging_out is not None:
-        staging_out["send"] = send_bufs
-        staging_out["recv"] = recv_bufs
+    """:func:`run_transpose_sim_many` with one field per rank (``n = 1`` is
+    the single-field staging layout): ``dests[r] <- srcs[r]``."""
+    return run_transpose_sim_many([[d] for d in dests], [[s] for s in srcs],
+                                  staging_out, wire_dtype=wire_dtype,
+                                  keep=keep, fill=fill)
 
 
 def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
                            staging_out=None, wire_dtype=None, keep=None,
                            fill="zero") -> None:
-    """:func:`run_transpose_sim` for ``n`` fields per rank with the
-    multi-field staging layout (plan.py): every field of a rank is packed
-    into ONE n-fold send buffer, and the exchange is ONE slice copy per peer
-    pair of ``n * c`` elements — the "one message per peer" contract.
+    """Every rank's transpose of ``n`` fields with the multi-field staging
+    layout (plan.py): every field of a rank is packed into ONE n-fold send
+    buffer, and the exchange is ONE slice copy per peer pair of ``n * c``
+    elements — the "one message per peer" contract.
     ``dests_per_rank[r][f]`` / ``srcs_per_rank[r][f]`` is field ``f`` on
     rank ``r``.  ``staging_out``, if a dict, receives the final
     ``send``/``recv`` buffers per rank (tests compare them).
-    ``wire_dtype``: a reduced-precision wire; the staging buffers then hold
-    wire scalars (bfloat16 as uint16 patterns), packs narrow, unpacks widen
-    and the local copy rounds.  ``keep`` / ``fill``: a truncated transpose
-    through the sub-box tables of the keep plan."""
+    ``wire_dtype``: a reduced-precision wire (see :class:`Transposition`);
+    the staging buffers then hold wire scalars (bfloat16 as uint16
+    patterns), packs narrow, unpacks widen and the local copy rounds.
+    ``keep`` / ``fill``: a truncated transpose; the staging buffers then hold
+    the kept elements only, a peer pair with nothing kept copies nothing, and
+    every field gets the zero fill."""
     _check_keep_wire(keep, wire_dtype)
-    if wire_dtype is not None:
-        return _run_sim_many_wire(dests_per_rank, srcs_per_rank, staging_out,
-                                  wire_dtype)
-    if keep is not None:
-        return _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out,
-                                  keep, fill)
     nranks = len(srcs_per_rank)
     n = len(srcs_per_rank[0])
     if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
             any(len(x) != n for x in dests_per_rank):
         raise ValueError("every rank needs the same number (>= 1) of fields")
-    plans = []
-    for r in range(nranks):
-        s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
-        aliased = any(_arrays_alias(s.data, d.data)
-                      for s in srcs_per_rank[r] for d in dests_per_rank[r])
-        plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
-                                aliased=aliased))
-    sflat = [[s.element_view() for s in row] for row in srcs_per_rank]
-    dflat = [[d.element_view() for d in row] for row in dests_per_rank]
-    dt = sflat[0][0].dtype
-    send_bufs, recv_bufs = [], []
-    for p in plans:
-        ns, nr = buffer_nelem_many(p, n)
-        send_bufs.append(np.empty(ns, dtype=dt))
-        recv_bufs.append(np.empty(nr, dtype=dt))
-
-    # pack every field on every rank (incl. staged self blocks) before any
-    # destination is written
-    for r, p in enumerate(plans):
-        for f in range(n):
-            for blk in p.peers:
-                if blk.pack is not None:
-                    apply_copy(copydesc_many(p, n, f, 1, blk.peer_k),
-                               sflat[r][f], send_bufs[r])
-            if p.self_pack is not None:
-                apply_copy(copydesc_many(p, n, f, 3), sflat[r][f],
-                           recv_bufs[r])
-    for r, p in enumerate(plans):
-        for f in range(n):
-            if p.local is not None:
-                apply_copy(p.local, sflat[r][f], dflat[r][f])
-            elif p.self_unpack is not None:
-                apply_copy(copydesc_many(p, n, f, 4), recv_bufs[r],
-                           dflat[r][f])
-
-    # exchange: ONE slice copy per peer pair, all n fields in it
-    for r, p in enumerate(plans):
-        if p.r_dim is None:
-            continue
-        for blk in p.peers:
-            if blk.peer_k == p.my_k or blk.send_nelem == 0:
-                continue
-            so, sn, _, _ = peer_message(p, n, blk.peer_k)
-            q = plans[blk.global_rank]
-            _, _, ro, rn = peer_message(q, n, p.my_k)
-            assert rn == sn, (r, blk.peer_k, sn, rn)
-            recv_bufs[blk.global_rank][ro:ro + rn] = send_bufs[r][so:so + sn]
-
-    # unpack every field on every rank
-    for r, p in enumerate(plans):
-        for f in range(n):
-            for blk in p.peers:
-                if blk.unpack is not None:
-                    apply_copy(copydesc_many(p, n, f, 2, blk.peer_k),
-                               recv_bufs[r], dflat[r][f])
-    if staging_out is not None:
-        staging_out["send"] = send_bufs
-        staging_out["recv"] = recv_bufs
-
-
-def _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out, keep,
-                       fill) -> None:
-    """run_transpose_sim_many on keep plans: the same stages over the
-    sub-box tables, one slice copy of the KEPT elements per peer pair (none
-    for a peer with nothing kept), and the zero fill of every field."""
-    nranks = len(srcs_per_rank)
-    n = len(srcs_per_rank[0])
-    if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
-            any(len(x) != n for x in dests_per_rank):
-        raise ValueError("every rank needs the same number (>= 1) of fields")
+    s00, d00 = srcs_per_rank[0][0], dests_per_rank[0][0]
+    codec = _codec(s00, _wire_pair(d00, s00, wire_dtype))
     plans = []
     for r in range(nranks):
         s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
@@ -704,28 +461,32 @@ def _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out, keep,
                       for s in srcs_per_rank[r] for d in dests_per_rank[r])
         plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
                                 aliased=aliased, keep=keep, fill=fill))
-    sflat = [[s.element_view() for s in row] for row in srcs_per_rank]
-    dflat = [[d.element_view() for d in row] for row in dests_per_rank]
-    dt = sflat[0][0].dtype
+    sflat = [[codec.view(s) for s in row] for row in srcs_per_rank]
+    dflat = [[codec.view(d) for d in row] for row in dests_per_rank]
+    dt, sc = codec.carrier or sflat[0][0].dtype, codec.scale
     send_bufs, recv_bufs = [], []
     for p in plans:
         ns, nr = buffer_nelem_many(p, n)
-        send_bufs.append(np.empty(ns, dtype=dt))
-        recv_bufs.append(np.empty(nr, dtype=dt))
+        send_bufs.append(np.empty(ns * sc, dtype=dt))
+        recv_bufs.append(np.empty(nr * sc, dtype=dt))
 
+    # pack every field on every rank (incl. staged self blocks) before any
+    # destination is written
     for r, p in enumerate(plans):
         for f in range(n):
             for which, d in stage_descs(p, n, f, 0):
-                apply_copy(d, sflat[r][f],
+                codec.copy(which, d, sflat[r][f],
                            send_bufs[r] if which == 1 else recv_bufs[r])
     for r, p in enumerate(plans):
         for f in range(n):
             for which, d in stage_descs(p, n, f, 1):
-                apply_copy(d, sflat[r][f] if which == 0 else recv_bufs[r],
+                codec.copy(which, d,
+                           sflat[r][f] if which == 0 else recv_bufs[r],
                            dflat[r][f])
             for fd in p.fills:
                 apply_fill(fd, dflat[r][f])
 
+    # exchange: ONE slice copy per peer pair, all n fields in it
     for r, p in enumerate(plans):
         if p.r_dim is None:
             continue
@@ -733,85 +494,18 @@ def _run_sim_many_keep(dests_per_rank, srcs_per_rank, staging_out, keep,
             if blk.peer_k == p.my_k or blk.send_nelem == 0:
                 continue
             so, sn, _, _ = peer_message(p, n, blk.peer_k)
+            # the matching recv block: the peer's block for MY coordinate
             q = plans[blk.global_rank]
             _, _, ro, rn = peer_message(q, n, p.my_k)
             assert rn == sn, (r, blk.peer_k, sn, rn)
-            recv_bufs[blk.global_rank][ro:ro + rn] = send_bufs[r][so:so + sn]
+            recv_bufs[blk.global_rank][ro * sc:(ro + rn) * sc] = \
+                send_bufs[r][so * sc:(so + sn) * sc]
 
+    # unpack every field on every rank
     for r, p in enumerate(plans):
         for f in range(n):
-            for _, d in stage_descs(p, n, f, 2):
-                apply_copy(d, recv_bufs[r], dflat[r][f])
-    if staging_out is not None:
-        staging_out["send"] = send_bufs
-        staging_out["recv"] = recv_bufs
-
-
-def _run_sim_many_wire(dests_per_rank, srcs_per_rank, staging_out,
-                       wire_dtype) -> None:
-    """run_transpose_sim_many with a reduced-precision wire: the same
-    staging layout in elements, every buffer in wire scalars."""
-    nranks = len(srcs_per_rank)
-    n = len(srcs_per_rank[0])
-    if n < 1 or any(len(x) != n for x in srcs_per_rank) or \
-            any(len(x) != n for x in dests_per_rank):
-        raise ValueError("every rank needs the same number (>= 1) of fields")
-    s00 = next(s for row in srcs_per_rank for s in row)
-    pair = _wire_pair(dests_per_rank[0][0], s00, wire_dtype)
-    nc = s00.ncomp * pair.comps
-    nar, wid, rnd = _wire_convs(pair)
-    plans = []
-    for r in range(nranks):
-        s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
-        aliased = any(_arrays_alias(s.data, d.data)
-                      for s in srcs_per_rank[r] for d in dests_per_rank[r])
-        plans.append(build_plan(s0.pencil, d0.pencil, r, s0.extra_dims,
-                                aliased=aliased))
-    sflat = [[s.data.view(pair.stored) for s in row] for row in srcs_per_rank]
-    dflat = [[d.data.view(pair.stored) for d in row]
-             for row in dests_per_rank]
-    send_bufs, recv_bufs = [], []
-    for p in plans:
-        ns, nr = buffer_nelem_many(p, n)
-        send_bufs.append(np.empty(ns * nc, dtype=pair.carrier))
-        recv_bufs.append(np.empty(nr * nc, dtype=pair.carrier))
-
-    for r, p in enumerate(plans):
-        for f in range(n):
-            for blk in p.peers:
-                if blk.pack is not None:
-                    apply_copy_conv(copydesc_many(p, n, f, 1, blk.peer_k),
-                                    sflat[r][f], send_bufs[r], nc, nar)
-            if p.self_pack is not None:
-                apply_copy_conv(copydesc_many(p, n, f, 3), sflat[r][f],
-                                recv_bufs[r], nc, nar)
-    for r, p in enumerate(plans):
-        for f in range(n):
-            if p.local is not None:
-                apply_copy_conv(p.local, sflat[r][f], dflat[r][f], nc, rnd)
-            elif p.self_unpack is not None:
-                apply_copy_conv(copydesc_many(p, n, f, 4), recv_bufs[r],
-                                dflat[r][f], nc, wid)
-
-    for r, p in enumerate(plans):
-        if p.r_dim is None:
-            continue
-        for blk in p.peers:
-            if blk.peer_k == p.my_k or blk.send_nelem == 0:
-                continue
-            so, sn, _, _ = peer_message(p, n, blk.peer_k)
-            q = plans[blk.global_rank]
-            _, _, ro, rn = peer_message(q, n, p.my_k)
-            assert rn == sn, (r, blk.peer_k, sn, rn)
-            recv_bufs[blk.global_rank][ro * nc:(ro + rn) * nc] = \
-                send_bufs[r][so * nc:(so + sn) * nc]
-
-    for r, p in enumerate(plans):
-        for f in range(n):
-            for blk in p.peers:
-                if blk.unpack is not None:
-                    apply_copy_conv(copydesc_many(p, n, f, 2, blk.peer_k),
-                                    recv_bufs[r], dflat[r][f], nc, wid)
+            for which, d in stage_descs(p, n, f, 2):
+                codec.copy(which, d, recv_bufs[r], dflat[r][f])
     if staging_out is not None:
         staging_out["send"] = send_bufs
         staging_out["recv"] = recv_bufs
