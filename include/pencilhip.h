@@ -88,8 +88,12 @@ void pa_comm_destroy(pa_comm *c);
  * Env PENCILHIP_EXCHANGE_CHUNKS=N (read at plan creation, default 1):
  * split the exchange into N chunk groups and unpack each chunk while later
  * chunks are in flight (the reference's Waitany overlap,
- * Transpositions.jl:510-517). */
+ * Transpositions.jl:510-517).
+ * flags bit 1 (PA_PLAN_GROUP_CVT): on a plan with a wire pair
+ * (pa_plan_create_wire) the converting kernels of a stage run as grouped
+ * launches, see there; on any other plan the bit has no effect. */
 #define PA_PLAN_ALIASED 1
+#define PA_PLAN_GROUP_CVT 2
 pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
                          int64_t elem_size, int e, const int64_t *extra_dims,
                          int rank, int flags, pa_plan **out);
@@ -141,13 +145,25 @@ pa_status pa_plan_create_comp(const pa_pencil *pin, const pa_pencil *pout,
  * the process grid, and since round_w is idempotent a chain x->y->z rounds
  * once.  pa_transpose_execute[_many], the three stage calls,
  * pa_transpose_wait, timing and PA_PLAN_ALIASED work on a wire plan.
- * PENCILHIP_EXCHANGE_CHUNKS does NOT apply: the exchange is a single group. */
+ * PENCILHIP_EXCHANGE_CHUNKS does NOT apply: the exchange is a single group.
+ * With PA_PLAN_GROUP_CVT in flags the PA_KERNEL_CVT_LINEAR entries of one
+ * stage with the same (op, scalars per access) share ONE grouped launch, and
+ * so do its PA_KERNEL_CVT_TILE entries of one op, in first-appearance order
+ * (the rule the ordinary plan applies to (kind, word));
+ * PA_KERNEL_CVT_GENERIC entries stay one launch each.  The selection per
+ * descriptor, the tables, the byte sizes and the result are those of the plan
+ * without the flag.  pa_transpose_execute then runs the n = 1 stage path
+ * (pa_transpose_execute_many), so a single field is grouped too; its
+ * hipMalloc fallback, sized in wire bytes, serves that path. */
 pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
                               int wire, int64_t ncomp, int e,
                               const int64_t *extra_dims, int rank, int flags,
                               pa_plan **out);
 /* The wire pair of a plan, or 0 for an ordinary plan. */
 int pa_plan_wire(const pa_plan *p);
+/* 1 for a plan with a wire pair created with PA_PLAN_GROUP_CVT, else 0 (an
+ * ordinary or keep plan ignores the flag). */
+int pa_plan_group_cvt(const pa_plan *p);
 
 /* Truncated transpose: move only a kept product set of indices — the other
  * standard lever of a pseudo-spectral code (after the 2/3 rule a third of the
@@ -321,7 +337,10 @@ pa_status pa_plan_copydesc_many(const pa_plan *p, int n, int f, int which,
  * Staging is taken from pa_plan_set_buffers, else assumed 256-byte aligned.
  * At most max_rows rows are written; *nrows is the full count.  The stage
  * calls execute exactly this list.  A wire plan reports its converting
- * kernels (PA_KERNEL_CVT_*) as ungrouped rows, one per descriptor.  A keep
+ * kernels (PA_KERNEL_CVT_*) as ungrouped rows, one per descriptor; created
+ * with PA_PLAN_GROUP_CVT it reports {PA_KERNEL_CVT_LINEAR or
+ * PA_KERNEL_CVT_TILE, 1, entries, workgroups} per signature, workgroups being
+ * the sum of the entries' grids, and PA_KERNEL_CVT_GENERIC rows as before.  A keep
  * plan has one entry per sub-box and field, and its local stage ends with
  * ONE grouped PA_KERNEL_FILL row holding the fill entries of every field. */
 #define PA_STAGE_PACK   0

@@ -787,17 +787,19 @@ template <typename T, int V> struct alignas(sizeof(T) * V) VecT { T v[V]; };
 /* Linear runs with conversion: axis 0 contiguous on both sides.  The
  * descriptor is in units of V SCALARS (the host folded ncomp into axis 0 and
  * checked that every access of V scalars is naturally aligned on both
- * sides); a lane converts V consecutive scalars per access. */
+ * sides); a lane converts V consecutive scalars per access.  The body is
+ * shared by k_cvt_linear and the grouped k_group_cvt_linear: b is the
+ * (entry-local) flat block id. */
 template <int WIRE, int OP, int V>
-__global__ __launch_bounds__(256) void k_cvt_linear(
-    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d)
+__device__ __forceinline__ void cvt_linear_body(const void *__restrict__ src_,
+                                                void *__restrict__ dst_,
+                                                const DescDev &d, int64_t b)
 {
     typedef CvtOp<WIRE, OP> C;
     typedef VecT<typename C::S, V> SV;
     typedef VecT<typename C::D, V> DV;
     const SV *__restrict__ src = (const SV *)src_;
     DV *__restrict__ dst = (DV *)dst_;
-    const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const int64_t run = d.dims[0];
     const int64_t idx = b * blockDim.x + threadIdx.x;
     if (idx >= d.total) return;
@@ -815,6 +817,14 @@ __global__ __launch_bounds__(256) void k_cvt_linear(
 #pragma unroll
     for (int k = 0; k < V; k++) out.v[k] = C::apply(in.v[k]);
     dst[doo] = out;
+}
+
+template <int WIRE, int OP, int V>
+__global__ __launch_bounds__(256) void k_cvt_linear(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d)
+{
+    cvt_linear_body<WIRE, OP, V>(src_, dst_, d,
+                                 (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 /* tile of the converting transpose: CVT_TILE_TJ elements along ta, and along
@@ -844,25 +854,26 @@ __host__ __device__ constexpr int cvt_tile_pitch(int nc)
  * written to LDS at j*PITCH + q; a dst row is nj*NC contiguous scalars, lane
  * q storing component q%NC of element q/NC from LDS j*PITCH + i*NC + q%NC.
  * Both phases are conflict-free (see cvt_tile_pitch).  The conversion is
- * split around the f32 LDS image: to_lds on load, from_lds on store. */
+ * split around the f32 LDS image: to_lds on load, from_lds on store.
+ *
+ * The body is shared by k_cvt_tile and the grouped k_group_cvt_tile: bid is
+ * the (entry-local) flat block id, already checked against the block count;
+ * tile is the workgroup's CVT_TILE_TJ * cvt_tile_pitch(NC) floats of LDS. */
 template <int WIRE, int OP, int NC>
-__global__ __launch_bounds__(1024) void k_cvt_tile(
-    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int ta,
-    int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+__device__ __forceinline__ void cvt_tile_body(
+    float *tile, const void *__restrict__ src_, void *__restrict__ dst_,
+    const DescDev &d, int ta, int64_t ntile_i, int64_t ntile_j, int64_t bid)
 {
     typedef CvtOp<WIRE, OP> C;
     typedef typename C::S S;
     typedef typename C::D D;
     constexpr int TI = cvt_tile_ti(NC), TJ = CVT_TILE_TJ, NR = 16;
     constexpr int PITCH = cvt_tile_pitch(NC);
-    __shared__ float tile[TJ * PITCH];
     const S *__restrict__ src = (const S *)src_;
     D *__restrict__ dst = (D *)dst_;
 
     const int tx = threadIdx.x; /* 0..63 */
     const int ty = threadIdx.y; /* 0..NR-1 */
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (bid >= nblocks) return;
     const int64_t t_i = bid % ntile_i;
     int64_t rest = bid / ntile_i;
     const int64_t t_j = rest % ntile_j;
@@ -908,6 +919,48 @@ __global__ __launch_bounds__(1024) void k_cvt_tile(
             }
         }
     }
+}
+
+template <int WIRE, int OP, int NC>
+__global__ __launch_bounds__(1024) void k_cvt_tile(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int ta,
+    int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+{
+    __shared__ float tile[CVT_TILE_TJ * cvt_tile_pitch(NC)];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    cvt_tile_body<WIRE, OP, NC>(tile, src_, dst_, d, ta, ntile_i, ntile_j,
+                                bid);
+}
+
+/* Grouped forms of the two kernels above (PA_PLAN_GROUP_CVT): one launch
+ * over a table of entries of one (op, V) resp. (op) signature, the wire pair
+ * and the component count being plan constants.  Entry lookup is that of the
+ * other grouped kernels; GEntry serves as is, njchunk carrying ntile_j. */
+template <int WIRE, int OP, int V>
+__global__ __launch_bounds__(256) void k_group_cvt_linear(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    cvt_linear_body<WIRE, OP, V>(g.src, g.dst, g.d, bid - first[e]);
+}
+
+template <int WIRE, int OP, int NC>
+__global__ __launch_bounds__(1024) void k_group_cvt_tile(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks)
+{
+    __shared__ float tile[CVT_TILE_TJ * cvt_tile_pitch(NC)];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    cvt_tile_body<WIRE, OP, NC>(tile, g.src, g.dst, g.d, g.ta, g.ntile_i,
+                                g.njchunk, bid - first[e]);
 }
 
 /* Elementwise converting fallback: descriptors with no contiguous axis, and
@@ -2026,6 +2079,9 @@ struct pa_plan {
      * an ordinary plan, (wire scalar bytes) * ncomp for a wire plan. */
     int wire = 0;
     int64_t msg_esz;
+    /* PA_PLAN_GROUP_CVT was given: on a wire plan the converting entries of
+     * a stage share grouped launches (build_stage); no effect otherwise */
+    bool group_cvt = false;
     int R;    /* -1 = same decomposition */
     int P;    /* subgroup size */
     int myk;  /* my coordinate along R */
@@ -2418,7 +2474,8 @@ static pa_status plan_build(const pa_pencil *pin, const pa_pencil *pout,
     pl->ncomp = ncomp;
     pl->msg_esz = pl->esz;
     pl->R = R;
-    pl->aliased = (flags & 1) != 0;
+    pl->aliased = (flags & PA_PLAN_ALIASED) != 0;
+    pl->group_cvt = (flags & PA_PLAN_GROUP_CVT) != 0;
     if (keep_lo) {
         /* the exchange of a keep plan is always a single group */
         pl->keep = true;
@@ -2859,6 +2916,11 @@ pa_status pa_plan_create_wire(const pa_pencil *pin, const pa_pencil *pout,
 
 int pa_plan_wire(const pa_plan *p) { return p ? p->wire : 0; }
 
+int pa_plan_group_cvt(const pa_plan *p)
+{
+    return p && p->wire && p->group_cvt ? 1 : 0;
+}
+
 pa_status pa_plan_create_keep(const pa_pencil *pin, const pa_pencil *pout,
                               int64_t scalar_size, int64_t ncomp, int e,
                               const int64_t *extra_dims, int rank, int flags,
@@ -2958,8 +3020,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
     }
 
     /* a keep plan runs the n = 1 stage path: pack -> exchange -> local +
-     * fill -> unpack (the fallback above is sized in kept elements) */
-    if (p->keep) {
+     * fill -> unpack (the fallback above is sized in kept elements); so does
+     * a wire plan with grouped converting kernels (sized in wire bytes) */
+    if (p->keep || pa_plan_group_cvt(p)) {
         const void *srcs[1] = {src_parent};
         void *dsts[1] = {dst_parent};
         return pa_transpose_execute_many(p, 1, srcs, dsts, stream_);
@@ -3302,6 +3365,7 @@ struct StageItem {
 
 struct StageLaunch {
     int kind = 0, word = 0;
+    int op = 0, vec = 0; /* grouped converting kinds: wire op, V (linear) */
     bool grouped = false;
     std::vector<int> items;
     int64_t nblocks = 0;
@@ -3390,7 +3454,8 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         it.src = src;
         it.dst = dst;
         if (p->wire) {
-            /* converting kernels: ungrouped rows, one launch per entry */
+            /* converting kernels: ungrouped rows, one launch per entry,
+             * unless the plan asks for grouped ones */
             const int op = which == 0 ? PA_WIRE_ROUND
                            : (which == 1 || which == 3) ? PA_WIRE_NARROW
                                                         : PA_WIRE_WIDEN;
@@ -3400,13 +3465,30 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
                 return st;
             it.nblocks = cvt_grid(it.c, &it.nti, &it.njc);
             if (it.nblocks == 0) return 0;
+            /* PA_PLAN_GROUP_CVT: linear entries of one (op, V) and tile
+             * entries of one op share a grouped launch */
+            const bool grp = p->group_cvt &&
+                             (it.c.kind == PA_KERNEL_CVT_LINEAR ||
+                              it.c.kind == PA_KERNEL_CVT_TILE);
+            const int vec = it.c.kind == PA_KERNEL_CVT_LINEAR ? it.c.V : 0;
+            const int idx = (int)t->items.size();
+            t->items.push_back(it);
+            if (grp)
+                for (auto &l : t->launches)
+                    if (l.grouped && l.kind == it.c.kind && l.op == op &&
+                        l.vec == vec) {
+                        l.items.push_back(idx);
+                        l.nblocks += it.nblocks;
+                        return 0;
+                    }
             StageLaunch l;
             l.kind = it.c.kind;
             l.word = 0;
-            l.grouped = false;
-            l.items.push_back((int)t->items.size());
+            l.op = op;
+            l.vec = vec;
+            l.grouped = grp;
+            l.items.push_back(idx);
             l.nblocks = it.nblocks;
-            t->items.push_back(it);
             t->launches.push_back(l);
             return 0;
         }
@@ -3547,10 +3629,10 @@ static pa_status upload_stage(StageTable *t)
             acc += it.nblocks;
             GEntry g;
             memset(&g, 0, sizeof g);
-            g.d = to_dev(it.k.d);
+            g.d = to_dev(it.cvt ? it.c.d : it.k.d);
             g.src = it.src;
             g.dst = it.dst;
-            g.ta = it.k.ta;
+            g.ta = it.cvt ? it.c.ta : it.k.ta;
             g.ntile_i = it.nti;
             g.njchunk = it.njc;
             memcpy(&ent[i], &g, sizeof g);
@@ -3562,7 +3644,40 @@ static pa_status upload_stage(StageTable *t)
     return 0;
 }
 
-static pa_status launch_group(const StageLaunch &l, hipStream_t stream)
+/* the grouped converting launch of (W, O): V resp. the component count pick
+ * the instance, as in launch_cvt_linear() and launch_cvt_sel() */
+template <int W, int O>
+static void launch_group_cvt(const StageLaunch &l, int ncomp, dim3 grid,
+                             hipStream_t stream, const int64_t *first,
+                             const GEntry *ent, int ne)
+{
+#define GROUP_CVT(kern, block)                                               \
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
+                       l.nblocks)
+    if (l.kind == PA_KERNEL_CVT_LINEAR) {
+        if constexpr (W != PA_WIRE_F64_F32) {
+            if (l.vec == 4) {
+                GROUP_CVT((k_group_cvt_linear<W, O, 4>), dim3(256));
+                return;
+            }
+        }
+        if (l.vec == 2)
+            GROUP_CVT((k_group_cvt_linear<W, O, 2>), dim3(256));
+        else
+            GROUP_CVT((k_group_cvt_linear<W, O, 1>), dim3(256));
+    } else if (ncomp == 1)
+        GROUP_CVT((k_group_cvt_tile<W, O, 1>), dim3(64, 16));
+    else if (ncomp == 2)
+        GROUP_CVT((k_group_cvt_tile<W, O, 2>), dim3(64, 16));
+    else if (ncomp == 3)
+        GROUP_CVT((k_group_cvt_tile<W, O, 3>), dim3(64, 16));
+    else
+        GROUP_CVT((k_group_cvt_tile<W, O, 4>), dim3(64, 16));
+#undef GROUP_CVT
+}
+
+static pa_status launch_group(const pa_plan *p, const StageLaunch &l,
+                              hipStream_t stream)
 {
     const int ne = (int)l.items.size();
     const int64_t *first = (const int64_t *)l.d_mem;
@@ -3576,6 +3691,21 @@ static pa_status launch_group(const StageLaunch &l, hipStream_t stream)
                            (const GFill *)((const char *)l.d_mem +
                                            ne * sizeof(int64_t)),
                            ne, l.nblocks);
+        HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    if (l.kind == PA_KERNEL_CVT_LINEAR || l.kind == PA_KERNEL_CVT_TILE) {
+        const bool lin = l.kind == PA_KERNEL_CVT_LINEAR;
+        if (lin ? (l.vec != 1 && l.vec != 2 &&
+                   !(l.vec == 4 && p->wire != PA_WIRE_F64_F32))
+                : (p->ncomp < 1 || p->ncomp > PA_CVT_TILE_MAX_COMP))
+            return fail("bad grouped converting launch");
+        if (pa_status gst = grid2d(l.nblocks, lin ? 256 : 64 * 16, &grid))
+            return gst;
+#define GROUP_CVT_WO(W, O)                                                   \
+    launch_group_cvt<W, O>(l, (int)p->ncomp, grid, stream, first, ent, ne)
+        CVT_FOR_WIRE_OP(p->wire, l.op, GROUP_CVT_WO)
+#undef GROUP_CVT_WO
         HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -3658,7 +3788,7 @@ static pa_status many_check(const pa_plan *p, int n, int stage,
         for (int f = 0; f < n; f++)
             if (!dsts[f]) return fail("null dst pointer for field %d", f);
     }
-    if (p->own_bufs && !(p->keep && n == 1))
+    if (p->own_bufs && !((p->keep || pa_plan_group_cvt(p)) && n == 1))
         return fail("multi-field stages need staging buffers of "
                     "pa_plan_buffer_sizes_many bytes from pa_plan_set_buffers");
     if ((p->send_total > 0 && !p->send_buf) ||
@@ -3699,7 +3829,7 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
     for (auto &l : t->launches) {
         pa_status st;
         if (l.grouped)
-            st = launch_group(l, stream);
+            st = launch_group(p, l, stream);
         else {
             const StageItem &it = t->items[l.items[0]];
             st = it.cvt ? launch_cvt_sel(it.c, it.src, it.dst, stream)

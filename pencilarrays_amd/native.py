@@ -107,6 +107,8 @@ class KernelKind(NamedTuple):
 
 
 STAGE_PACK, STAGE_LOCAL, STAGE_UNPACK = 0, 1, 2
+# flags of the plan creators
+PLAN_ALIASED, PLAN_GROUP_CVT = 1, 2
 
 
 class StageLaunch(NamedTuple):
@@ -251,13 +253,15 @@ class NativePlan:
     def __init__(self, Pi, Po, rank: int, elem_size: int,
                  extra_dims: Tuple[int, ...] = (), aliased: bool = False,
                  ncomp: int = 1, wire: Optional[int] = None,
-                 keep=None, fill: int = FILL_ZERO):
+                 keep=None, fill: int = FILL_ZERO, group_cvt: bool = False):
         """``ncomp > 1``: elements of ``ncomp`` scalars of ``elem_size``
         bytes, components fastest (pa_plan_create_comp).  ``wire``: a wire
         pair code (WIRE_F64_F32, ...) for a reduced-precision wire plan
         (pa_plan_create_wire); ``elem_size`` is then the stored scalar
         size.  ``keep``: ``(a, b)`` per logical dim for a truncated transpose
-        (pa_plan_create_keep) with ``fill`` FILL_ZERO or FILL_NONE."""
+        (pa_plan_create_keep) with ``fill`` FILL_ZERO or FILL_NONE.
+        ``group_cvt``: set PA_PLAN_GROUP_CVT, which on a wire plan groups the
+        converting kernels of a stage and has no effect on any other plan."""
         if keep is not None and wire is not None:
             raise ValueError(
                 "a keep set together with a wire pair is not supported")
@@ -291,6 +295,8 @@ class NativePlan:
         self.ncomp = int(ncomp)
         self.wire = wire
         self.keep = None
+        flags = (PLAN_ALIASED if aliased else 0) | \
+            (PLAN_GROUP_CVT if group_cvt else 0)
         if keep is not None:
             keep = list(keep)
             nk = len(keep)
@@ -305,7 +311,7 @@ class NativePlan:
             _check(lib, lib.pa_plan_create_keep(
                 self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
                 (I64 * e)(*extra_dims) if e else None, rank,
-                1 if aliased else 0,
+                flags,
                 (I64 * nk)(*[a for a, _ in self.keep]),
                 (I64 * nk)(*[b for _, b in self.keep]), int(fill),
                 ctypes.byref(self._plan)), "pa_plan_create_keep")
@@ -313,7 +319,7 @@ class NativePlan:
             _check(lib, lib.pa_plan_create_comp(
                 self._pi, self._po, I64(elem_size), I64(self.ncomp), e,
                 (I64 * e)(*extra_dims) if e else None, rank,
-                1 if aliased else 0,
+                flags,
                 ctypes.byref(self._plan)), "pa_plan_create_comp")
         else:
             if WIRE_STORED_BYTES.get(wire, elem_size) != elem_size:
@@ -323,7 +329,7 @@ class NativePlan:
             _check(lib, lib.pa_plan_create_wire(
                 self._pi, self._po, int(wire), I64(self.ncomp), e,
                 (I64 * e)(*extra_dims) if e else None, rank,
-                1 if aliased else 0,
+                flags,
                 ctypes.byref(self._plan)), "pa_plan_create_wire")
         self.nproc_sub = lib.pa_plan_nproc_sub(self._plan)
         self.r_dim = lib.pa_plan_r_dim(self._plan)
@@ -333,6 +339,11 @@ class NativePlan:
         """The plan's wire pair code, 0 for an ordinary plan
         (pa_plan_wire)."""
         return int(self.lib.pa_plan_wire(self._plan))
+
+    def group_cvt(self) -> bool:
+        """True on a wire plan created with ``group_cvt=True``
+        (pa_plan_group_cvt)."""
+        return bool(self.lib.pa_plan_group_cvt(self._plan))
 
     def buffer_sizes(self) -> Tuple[int, int]:
         s, r = I64(), I64()
@@ -717,9 +728,10 @@ def staging_pool(device) -> StagingPool:
     return _POOLS[idx]
 
 
-def _native_plan_for(plan, src, pair) -> NativePlan:
+def _native_plan_for(plan, src, pair, group_cvt: bool = False) -> NativePlan:
     """The native plan of a (Multi)Transposition over arrays like ``src``;
-    ``pair`` is its wire.WirePair or None."""
+    ``pair`` is its wire.WirePair or None, ``group_cvt`` its
+    ``wire_grouped``."""
     if pair is None:
         return NativePlan(plan.Pi, plan.Po, plan.rank,
                           src.data.element_size(), plan.extra_dims,
@@ -727,7 +739,8 @@ def _native_plan_for(plan, src, pair) -> NativePlan:
                           keep=plan.keep, fill=plan.fill)
     return NativePlan(plan.Pi, plan.Po, plan.rank, pair.stored.itemsize,
                       plan.extra_dims, aliased=plan.aliased,
-                      ncomp=src.ncomp * pair.comps, wire=pair.code)
+                      ncomp=src.ncomp * pair.comps, wire=pair.code,
+                      group_cvt=group_cvt)
 
 
 class NativeTransposition:
@@ -740,7 +753,8 @@ class NativeTransposition:
         plan = t.plan
         src = t.src
         self.np_plan = plan
-        self.native = _native_plan_for(plan, src, getattr(t, "wire", None))
+        self.native = _native_plan_for(plan, src, getattr(t, "wire", None),
+                                       getattr(t, "wire_grouped", False))
         sb, rb = self.native.buffer_sizes()
         dev = src.data.device
         # Staging comes from the per-device shared pool (the reference's
@@ -798,7 +812,8 @@ class NativeMultiTransposition:
         plan = mt.plan
         src = mt.srcs[0]
         self.n = len(mt.srcs)
-        self.native = _native_plan_for(plan, src, getattr(mt, "wire", None))
+        self.native = _native_plan_for(plan, src, getattr(mt, "wire", None),
+                                       getattr(mt, "wire_grouped", False))
         sb, rb = self.native.buffer_sizes_many(self.n)
         dev = src.data.device
         self._need = (max(sb, 1), max(rb, 1))

@@ -62,6 +62,13 @@ def _check_keep_wire(keep, wire_dtype):
             "transpose moves the stored type")
 
 
+def _check_wire_grouped(wire_grouped, wire_dtype):
+    if wire_grouped and wire_dtype is None:
+        raise ValueError(
+            "wire_grouped=True needs a wire_dtype: it groups the converting "
+            "kernels of a reduced-precision wire")
+
+
 class _Codec(NamedTuple):
     """The two things in which the host mirror of a reduced-precision wire
     differs from the plain one: how an array and the staging buffers are
@@ -131,7 +138,7 @@ def _arrays_alias(a, b) -> bool:
 class Transposition:
     def __init__(self, dest: PencilArray, src: PencilArray,
                  method: str = "grouped", wire_dtype=None, keep=None,
-                 fill="zero"):
+                 fill="zero", wire_grouped: bool = False):
         """``Transposition(Ao, Ai; method)`` (Transpositions.jl:94-119).
 
         ``keep`` (``(a, b)`` per logical dim, ``None`` entries meaning full;
@@ -147,6 +154,11 @@ class Transposition:
         ``dest == T(round_wire(src))`` whatever the process grid
         (pa_plan_create_wire).  complex128 with float32 is complex64 on the
         wire.  ``None`` moves the bytes as they are.
+
+        ``wire_grouped=True`` (only with ``wire_dtype``) runs the converting
+        kernels of each stage as grouped launches on the GPU
+        (PA_PLAN_GROUP_CVT); the result is the same bit for bit, and the
+        numpy host mirror, which has no launches, ignores it.
 
         ``method`` is accepted for signature parity with the reference's
         PointToPoint/Alltoallv choice (:56-68): on MI355X both map to the
@@ -168,8 +180,10 @@ class Transposition:
         if method not in ("grouped", "point_to_point", "alltoallv"):
             raise ValueError(f"unknown transpose method {method!r}")
         _check_keep_wire(keep, wire_dtype)
+        _check_wire_grouped(wire_grouped, wire_dtype)
         self.method = method
         self.wire = _wire_pair(dest, src, wire_dtype)
+        self.wire_grouped = bool(wire_grouped)
         self.src = src
         self.dest = dest
         self.aliased = _arrays_alias(src.data, dest.data)
@@ -271,12 +285,14 @@ class Transposition:
 
 def transpose_into(dest: PencilArray, src: PencilArray,
                    method: str = "grouped", wire_dtype=None, keep=None,
-                   fill="zero") -> PencilArray:
+                   fill="zero", wire_grouped: bool = False) -> PencilArray:
     """``transpose!(dest, src; method)`` (Transpositions.jl:161-169)."""
+    _check_wire_grouped(wire_grouped, wire_dtype)
     if dest is src:
         return dest
     return Transposition(dest, src, method=method, wire_dtype=wire_dtype,
-                         keep=keep, fill=fill).execute()
+                         keep=keep, fill=fill,
+                         wire_grouped=wire_grouped).execute()
 
 
 class MultiTransposition:
@@ -297,13 +313,15 @@ class MultiTransposition:
     field, which pins the semantics, not the performance.
 
     ``wire_dtype``: a reduced-precision wire for every field, as in
-    :class:`Transposition`.  ``keep`` / ``fill``: a truncated transpose of
+    :class:`Transposition`; ``wire_grouped``: its converting kernels as
+    grouped launches, likewise.  ``keep`` / ``fill``: a truncated transpose of
     every field, as in :class:`Transposition`."""
 
     def __init__(self, dests: Sequence[PencilArray],
                  srcs: Sequence[PencilArray], wire_dtype=None, keep=None,
-                 fill="zero"):
+                 fill="zero", wire_grouped: bool = False):
         _check_keep_wire(keep, wire_dtype)
+        _check_wire_grouped(wire_grouped, wire_dtype)
         dests, srcs = list(dests), list(srcs)
         if len(dests) != len(srcs):
             raise ValueError(
@@ -352,6 +370,7 @@ class MultiTransposition:
         self.srcs = srcs
         self.dests = dests
         self.wire_dtype = wire_dtype
+        self.wire_grouped = bool(wire_grouped)
         self.keep, self.fill = keep, fill
         self.wire = _wire_pair(d0, s0, wire_dtype)
         self.aliased = any(_arrays_alias(s.data, d.data)
@@ -372,7 +391,8 @@ class MultiTransposition:
             srcs = self.srcs
         for d, s in zip(self.dests, srcs):
             Transposition(d, s, wire_dtype=self.wire_dtype, keep=self.keep,
-                          fill=self.fill).execute()
+                          fill=self.fill,
+                          wire_grouped=self.wire_grouped).execute()
 
     def execute(self, sync: bool = True):
         """Run the transposes; ``sync=False`` returns with the work enqueued
@@ -402,10 +422,10 @@ class MultiTransposition:
 
 def transpose_many_into(dests: Sequence[PencilArray],
                         srcs: Sequence[PencilArray], wire_dtype=None,
-                        keep=None, fill="zero"):
+                        keep=None, fill="zero", wire_grouped: bool = False):
     """``transpose!`` of every pair ``dests[i] <- srcs[i]`` in one call."""
     return MultiTransposition(dests, srcs, wire_dtype=wire_dtype, keep=keep,
-                              fill=fill).execute()
+                              fill=fill, wire_grouped=wire_grouped).execute()
 
 
 # ----------------------------------------------------------------------
@@ -417,18 +437,19 @@ def transpose_many_into(dests: Sequence[PencilArray],
 def run_transpose_sim(dests: Sequence[PencilArray],
                       srcs: Sequence[PencilArray],
                       staging_out=None, wire_dtype=None, keep=None,
-                      fill="zero") -> None:
+                      fill="zero", wire_grouped: bool = False) -> None:
     """:func:`run_transpose_sim_many` with one field per rank (``n = 1`` is
     the single-field staging layout): ``dests[r] <- srcs[r]``."""
     return run_transpose_sim_many([[d] for d in dests], [[s] for s in srcs],
                                   staging_out, wire_dtype=wire_dtype,
-                                  keep=keep, fill=fill)
+                                  keep=keep, fill=fill,
+                                  wire_grouped=wire_grouped)
 
 
 def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
                            staging_out=None, wire_dtype=None, keep=None,
-                           fill="zero") -> None:
+                           fill="zero", wire_grouped: bool = False) -> None:
     """Every rank's transpose of ``n`` fields with the multi-field staging
     layout (plan.py): every field of a rank is packed into ONE n-fold send
     buffer, and the exchange is ONE slice copy per peer pair of ``n * c``
@@ -441,8 +462,10 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
     patterns), packs narrow, unpacks widen and the local copy rounds.
     ``keep`` / ``fill``: a truncated transpose; the staging buffers then hold
     the kept elements only, a peer pair with nothing kept copies nothing, and
-    every field gets the zero fill."""
+    every field gets the zero fill.  ``wire_grouped`` is accepted for parity
+    with :class:`Transposition`: the host mirror has no launches to group."""
     _check_keep_wire(keep, wire_dtype)
+    _check_wire_grouped(wire_grouped, wire_dtype)
     nranks = len(srcs_per_rank)
     n = len(srcs_per_rank[0])
     if n < 1 or any(len(x) != n for x in srcs_per_rank) or \

@@ -7,17 +7,24 @@ bf16 wire at 512^3 for n = 1.  Per case the pack, local and unpack stage
 calls (pa_transpose_{pack,local,unpack}_many) of
 
   (a) the ordinary plan (code the wire option does not touch: the yardstick),
-  (b) the wire plan: NARROW packs, ROUND local copy, WIDEN unpacks.
+  (b) the wire plan: NARROW packs, ROUND local copy, WIDEN unpacks, one
+      launch per descriptor,
+  (c) the wire plan created with PA_PLAN_GROUP_CVT: the same kernels' bodies
+      in one grouped launch per stage and signature.
 
 World-1 case: the whole 512^3 permuted x->y transpose (pa_transpose_execute),
-ordinary against the wire plan, which is one ROUND copy — what a single-GPU
+ordinary against the two wire plans, each one ROUND copy — what a single-GPU
 user pays for the option.
 
-(a) and (b) run in ONE process, alternating a, b, a, b, ..., each sample
-timed with HIP events around the whole stage, after a warm-up of every shape.
-Reported: median of REPS samples with min..max in us, and GB/s of the bytes
-the stage actually moves (read + written) over the median.  The exchange is
-not run: one GPU has nobody to exchange with.
+(a), (b) and (c) run in ONE process, alternating a, b, c, a, b, c, ..., each
+sample timed with HIP events around the whole stage, after a warm-up of every
+shape.  Reported: median of REPS samples with min..max in us, GB/s of the
+bytes the stage actually moves (read + written) over the median, and for (c)
+against (b) and against (a) whether its median is at or below the other's or
+the min..max ranges overlap ("met") or not ("not met").  After the timing the
+stages of (b) and (c) run once more on the same inputs and their staging and
+destinations are compared byte for byte.  The exchange is not run: one GPU
+has nobody to exchange with.
 
 Without --case this is a driver: every case runs as a child process under
 its own time limit, one after the other, and the first non-zero status stops
@@ -66,30 +73,36 @@ def stats(xs):
     return statistics.median(xs), min(xs), max(xs)
 
 
-def ab(fa, fb, reps, warmup):
+def abc(fns, reps, warmup):
     for _ in range(warmup):
-        fa()
-        fb()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    ta, tb = [], []
+    ts = [[] for _ in fns]
     for _ in range(reps):
-        ta.append(timed(fa))
-        tb.append(timed(fb))
+        for t, fn in zip(ts, fns):
+            t.append(timed(fn))
     torch.cuda.synchronize()
-    return stats(ta), stats(tb)
+    return [stats(t) for t in ts]
 
 
-def line(name, stage, sa, sb, bytes_a, bytes_b, kinds_a, kinds_b):
-    (ma, la, ha), (mb, lb, hb) = sa, sb
-    apart = lb > ha or hb < la
-    verdict = ("wire above, ranges apart" if mb > ma and apart else
-               "wire below, ranges apart" if mb < ma and apart else
-               "ranges overlap")
-    return (f"{name} {stage:6s} ordinary {kinds_a} {ma:8.1f} "
-            f"({la:.1f}..{ha:.1f}) {bytes_a / 1e3 / ma:6.0f} GB/s | wire "
-            f"{kinds_b} {mb:8.1f} ({lb:.1f}..{hb:.1f}) "
-            f"{bytes_b / 1e3 / mb:6.0f} GB/s | wire/ordinary {mb / ma:.3f} "
-            f"| {verdict}")
+def met(sc, so):
+    """(c) against another leg: met when its median is at or below the
+    other's, or the two min..max ranges overlap."""
+    (mc, lc, hc), (mo, lo, ho) = sc, so
+    return "met" if mc <= mo or not (lc > ho or hc < lo) else "not met"
+
+
+def line(name, stage, st, nbytes, kinds):
+    sa, sb, sc = st
+    legs = " | ".join(
+        f"{leg} {k} {m:8.1f} ({lo:.1f}..{hi:.1f}) {nb / 1e3 / m:6.0f} GB/s"
+        for leg, k, (m, lo, hi), nb in zip(
+            ("(a) ordinary", "(b) wire", "(c) wire grouped"), kinds, st,
+            nbytes))
+    return (f"{name} {stage:6s} {legs} | b/a {sb[0] / sa[0]:.3f} c/a "
+            f"{sc[0] / sa[0]:.3f} c/b {sc[0] / sb[0]:.3f} | c<=b "
+            f"{met(sc, sb)} | c<=a {met(sc, sa)}")
 
 
 def kinds_of(rows):
@@ -116,12 +129,14 @@ def run_slab(name, N, n, elem, reps, warmup, out):
     pyp = build_plan(Pi, Po, 0)
     pa = native.NativePlan(Pi, Po, 0, ssz)
     pb = native.NativePlan(Pi, Po, 0, ssz, wire=code)
+    pc = native.NativePlan(Pi, Po, 0, ssz, wire=code, group_cvt=True)
+    plans = (pa, pb, pc)
     srcs = [torch.randn(Pi.length_local(0), dtype=tdt, device="cuda:0")
             for _ in range(n)]
     dsts = [torch.zeros(Po.length_local(0), dtype=tdt, device="cuda:0")
             for _ in range(n)]
     bufs = []
-    for p in (pa, pb):
+    for p in plans:
         sb, rb = p.buffer_sizes_many(n)
         send = torch.zeros(sb, dtype=torch.uint8, device="cuda:0")
         # finite wire values to widen: zeros would do, ones show in a diff
@@ -144,12 +159,27 @@ def run_slab(name, N, n, elem, reps, warmup, out):
          n_unpack * 2 * ssz, n_unpack * (ssz + wsz)),
     ]
     for sname, stage, mk, bytes_a, bytes_b in stages:
-        sa, sb_ = ab(mk(pa), mk(pb), reps, warmup)
-        out(line(name, sname, sa, sb_, bytes_a, bytes_b,
-                 kinds_of(pa.stage_launches(n, stage, sp, dp)),
-                 kinds_of(pb.stage_launches(n, stage, sp, dp))))
-    for p in (pa, pb):
+        out(line(name, sname, abc([mk(p) for p in plans], reps, warmup),
+                 (bytes_a, bytes_b, bytes_b),
+                 [kinds_of(p.stage_launches(n, stage, sp, dp))
+                  for p in plans]))
+    # (c) computes what (b) computes: every stage once more, same inputs
+    res = []
+    for p, (send, recv) in zip(plans[1:], bufs[1:]):
+        for t in dsts:
+            t.zero_()
+        p.pack_many(sp)
+        p.local_many(sp, dp)
+        p.unpack_many(dp)
+        torch.cuda.synchronize()
+        res.append([send.clone()] + [t.clone() for t in dsts])
+    same = all(torch.equal(x.view(torch.uint8), y.view(torch.uint8))
+               for x, y in zip(*res))
+    out(f"{name} (c) staging and destinations == (b), byte for byte: {same}")
+    for p in plans:
         p.set_buffers(0, 0)
+    if not same:
+        sys.exit("grouped wire output differs from the ungrouped one")
 
 
 def run_world1(name, N, elem, reps, warmup, out):
@@ -160,22 +190,24 @@ def run_world1(name, N, elem, reps, warmup, out):
     Po = Pencil(topo, dims, (0, 2), permute=(1, 2, 0))
     pa = native.NativePlan(Pi, Po, 0, ssz)
     pb = native.NativePlan(Pi, Po, 0, ssz, wire=code)
+    pc = native.NativePlan(Pi, Po, 0, ssz, wire=code, group_cvt=True)
+    plans = (pa, pb, pc)
     src = torch.randn(Pi.length_local(0), dtype=tdt, device="cuda:0")
-    da = torch.zeros_like(src)
-    db = torch.zeros_like(src)
-    sa, sb_ = ab(lambda: pa.execute(src.data_ptr(), da.data_ptr(), 0),
-                 lambda: pb.execute(src.data_ptr(), db.data_ptr(), 0),
-                 reps, warmup)
+    ds = [torch.zeros_like(src) for _ in plans]
+    st = abc([(lambda p=p, d=d: p.execute(src.data_ptr(), d.data_ptr(), 0))
+              for p, d in zip(plans, ds)], reps, warmup)
     nbytes = 2 * ssz * src.numel()
-    sp, dp = [src.data_ptr()], [da.data_ptr()]
-    out(line(name, "whole", sa, sb_, nbytes, nbytes,
-             kinds_of(pa.stage_launches(1, native.STAGE_LOCAL, sp, dp)),
-             kinds_of(pb.stage_launches(1, native.STAGE_LOCAL, sp, dp))))
-    # the wire result is the ordinary one, rounded
-    same = torch.equal(db, da.to(torch.float32).to(tdt)) \
+    sp, dp = [src.data_ptr()], [ds[0].data_ptr()]
+    out(line(name, "whole", st, (nbytes,) * 3,
+             [kinds_of(p.stage_launches(1, native.STAGE_LOCAL, sp, dp))
+              for p in plans]))
+    # the wire result is the ordinary one, rounded; (c) is (b)
+    same = torch.equal(ds[1], ds[0].to(torch.float32).to(tdt)) \
         if code == native.WIRE_F64_F32 else None
     out(f"{name} wire output == round(ordinary output): {same}")
-    if same is False:
+    same_c = torch.equal(ds[2].view(torch.uint8), ds[1].view(torch.uint8))
+    out(f"{name} (c) output == (b), byte for byte: {same_c}")
+    if same is False or not same_c:
         sys.exit("wire output differs from the rounded ordinary output")
 
 
@@ -203,10 +235,14 @@ def main():
 
     lines = [
         f"# tools/wire_bench.py; rank 0; median of {args.reps} (min..max), "
-        f"us; ordinary/wire alternating in one process per case, HIP events "
+        f"us; (a)/(b)/(c) alternating in one process per case, HIP events "
         f"around the whole stage; GB/s = bytes read + written / median",
-        "# ordinary = the plan without a wire pair; wire = NARROW packs, "
-        "ROUND local, WIDEN unpacks; the exchange is not run (one GPU)",
+        "# (a) ordinary = the plan without a wire pair; (b) wire = NARROW "
+        "packs, ROUND local, WIDEN unpacks, one launch per descriptor; (c) = "
+        "(b) created with PA_PLAN_GROUP_CVT; the exchange is not run (one "
+        "GPU)",
+        "# c<=b / c<=a: met = (c)'s median at or below the other's, or the "
+        "min..max ranges overlap",
     ]
     print("\n".join(lines), flush=True)
     for i in range(len(CASES)):
