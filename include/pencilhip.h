@@ -165,6 +165,53 @@ int pa_plan_wire(const pa_plan *p);
  * ordinary or keep plan ignores the flag). */
 int pa_plan_group_cvt(const pa_plan *p);
 
+/* Scaled transpose: dest = alpha * T(src), the normalisation of an inverse
+ * FFT folded into the pass that writes the destination anyway (the reference
+ * has no such option: PencilFFTs scales in a broadcast of its own after the
+ * last transpose).  Real scalar types of a scale: */
+#define PA_SCALAR_F32 1 /* float32 */
+#define PA_SCALAR_F64 2 /* float64 */
+/* pa_plan_set_scale is valid on a plan of pa_plan_create, pa_plan_create_comp
+ * or pa_plan_create_keep whose element size is a multiple of the scalar
+ * size; an element is then nscal = element bytes / scalar bytes scalars
+ * (a complex element two, elem_dims multiply in).
+ * Contract: with S the scalar type, a = S(alpha) (alpha rounded to nearest
+ * even) and T the transposition of the same plan without a scale,
+ *     dest == T(src (*) a)   bit for bit on every non-NaN scalar,
+ * NaN staying NaN with sign and payload unspecified; (*) is ONE IEEE
+ * multiply per real scalar: round to nearest even, subnormals kept, +-0 and
+ * +-inf by the IEEE rules.  A complex element is scaled component by
+ * component; it is not a complex multiply.  Every element is multiplied
+ * exactly once, on the DESTINATION side: the fused local copy, the aliased
+ * self unpack and every unpack.  Packs and the aliased self pack stay the
+ * ordinary kernels, so staging buffers and messages carry unscaled bytes,
+ * identical to those of the plan without a scale (a host that runs its own
+ * exchange through the stage calls sees no difference), and the result does
+ * not depend on the process grid.  On a keep plan dest[i] = a * src[i] for i
+ * in K; the fill is unchanged.
+ * alpha == 1.0 means "no scale": the plan then runs exactly the code, tables
+ * and launches it runs without this call, and pa_plan_scale returns 0.
+ * alpha is a kernel argument and not part of the stage tables: a change
+ * between two values != 1 keeps the cached tables, a change between scaled
+ * and unscaled drops them (pa_plan_stage_table_count becomes 0).
+ * A scaled plan's descriptors, byte sizes and pack launches are those of the
+ * plan without a scale.  Its local and unpack copies run the scaling kernels
+ * (pa_copy_kernel_kind_scale per descriptor), grouped from the start: the
+ * PA_KERNEL_SCALE_LINEAR entries of one stage with the same scalars per
+ * access share ONE launch, and so do its PA_KERNEL_SCALE_TILE entries, in
+ * first-appearance order; PA_KERNEL_SCALE_GENERIC entries stay one launch
+ * each; a keep plan's grouped PA_KERNEL_FILL launch stays as it is.
+ * pa_transpose_execute runs the n = 1 stage path (pa_transpose_execute_many)
+ * and PENCILHIP_EXCHANGE_CHUNKS does not apply.  pa_transpose_execute_many,
+ * the three stage calls, pa_transpose_wait, timing and PA_PLAN_ALIASED work.
+ * Errors: a plan with a wire pair (that would be two roundings per element
+ * and another contract; left out deliberately), an unknown scalar code, an
+ * element size that is no multiple of the scalar size, a NaN or infinite
+ * alpha. */
+pa_status pa_plan_set_scale(pa_plan *p, int scalar, double alpha);
+/* 1 for a scaled plan (*scalar, *alpha written where non-NULL), else 0. */
+int pa_plan_scale(const pa_plan *p, int *scalar, double *alpha);
+
 /* Truncated transpose: move only a kept product set of indices — the other
  * standard lever of a pseudo-spectral code (after the 2/3 rule a third of the
  * modes along every transformed dimension are known zeros; the reference has
@@ -487,6 +534,43 @@ pa_status pa_copy_kernel_kind_wire(int nd, const int64_t *dims,
                                    int wire, int op, int64_t ncomp,
                                    const void *src, const void *dst,
                                    int64_t out[5]);
+
+/* ---- scaling copies (scaled transposes) -------------------------------- */
+/* One strided-copy descriptor with a multiply (the kernels a scaled plan
+ * uses): dst = src * S(alpha) per real scalar.  Strides, offsets and dims in
+ * ELEMENTS of nscal scalars of type `scalar` (PA_SCALAR_*), scalars of an
+ * element fastest.  Both pointers must be aligned to the scalar; wider
+ * accesses are used only where the pointers, offsets and strides allow them.
+ * alpha must be finite; alpha == 1.0 still runs the scaling kernel. */
+pa_status pa_device_copy_scale(int nd, const int64_t *dims,
+                               const int64_t *sstr, int64_t soff,
+                               const int64_t *dstr, int64_t doff, int scalar,
+                               int64_t nscal, double alpha, const void *src,
+                               void *dst, void *stream);
+/* Which scaling kernel runs for this descriptor (host-only; pointers are
+ * used for their alignment only).  out = {kind, V, tile_i, tile_j,
+ * sweep_depth}, the rules of pa_copy_kernel_kind_wire:
+ *  - axis 0 contiguous on both sides (1-D included): PA_KERNEL_SCALE_LINEAR,
+ *    a lane moving V consecutive scalars per access.  V starts at
+ *    16 / scalar bytes and is halved down to 1 until it divides the scalar
+ *    run dims[0]*nscal and the base pointer, the offset and every non-unit
+ *    stride of BOTH sides, in scalars;
+ *  - src contiguous along axis 0, dst along an axis ta >= 1, nscal <= 4:
+ *    PA_KERNEL_SCALE_TILE, an LDS transpose of tile_i (axis 0) x tile_j (ta)
+ *    elements holding the scalar type in LDS (rows of 512 bytes: tile_i =
+ *    128 / nscal for f32 and 64 / nscal for f64, tile_j = 64);
+ *  - otherwise PA_KERNEL_SCALE_GENERIC, elementwise: correct and slow;
+ *  - an empty descriptor: PA_KERNEL_NONE.
+ * V = 1 and tile = 0 where they do not apply; sweep_depth is 1. */
+#define PA_KERNEL_SCALE_LINEAR  13
+#define PA_KERNEL_SCALE_TILE    14
+#define PA_KERNEL_SCALE_GENERIC 15
+pa_status pa_copy_kernel_kind_scale(int nd, const int64_t *dims,
+                                    const int64_t *sstr, int64_t soff,
+                                    const int64_t *dstr, int64_t doff,
+                                    int scalar, int64_t nscal,
+                                    const void *src, const void *dst,
+                                    int64_t out[5]);
 
 /* ---- zero fill (truncated transposes) ---------------------------------- */
 /* Zero one destination-only window on the device (the kernel body a keep

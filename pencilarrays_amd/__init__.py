@@ -32,6 +32,7 @@ from .transpositions import (
     transpose_many_into,
 )
 from .wire import round_wire
+from .scale import scale_array
 from .multiarrays import ManyPencilArray
 from .pencilio import MPIIOFile
 from . import reductions
@@ -45,7 +46,7 @@ __all__ = [
     "Topology", "dims_create", "Pencil", "PencilArray",
     "Transposition", "transpose_into", "run_transpose_sim", "ManyPencilArray",
     "MultiTransposition", "transpose_many_into", "run_transpose_sim_many",
-    "MPIIOFile", "reductions", "round_wire",
+    "MPIIOFile", "reductions", "round_wire", "scale_array",
     "gather", "gather_sim", "gather_dist",
     "CopyDesc", "TransposePlan", "build_plan", "normalize_desc",
     "FillDesc", "fourier_keep",

@@ -990,6 +990,199 @@ __global__ __launch_bounds__(256) void k_cvt_generic(
     }
 }
 
+/* ---- scaling kernels: dest = alpha * T(src) ------------------------------
+ *
+ * A scaled plan (pa_plan_set_scale) multiplies every real scalar S (float or
+ * double) by a = S(alpha) in the pass that writes the destination: the fused
+ * local copy and the unpacks.  One IEEE multiply per scalar in the default
+ * kernel float mode (round to nearest even, subnormals kept).  The kernels
+ * are the converting family's with S on both sides and the multiply in place
+ * of the conversion; descriptors stay in ELEMENT units of NC scalars. */
+template <typename S, int V>
+__device__ __forceinline__ void scale_linear_body(
+    const void *__restrict__ src_, void *__restrict__ dst_, const DescDev &d,
+    int64_t b, S a)
+{
+    typedef VecT<S, V> SV;
+    const SV *__restrict__ src = (const SV *)src_;
+    SV *__restrict__ dst = (SV *)dst_;
+    const int64_t run = d.dims[0];
+    const int64_t idx = b * blockDim.x + threadIdx.x;
+    if (idx >= d.total) return;
+    int64_t o = idx / run;
+    const int64_t i = idx - o * run;
+    int64_t so = d.soff + i, doo = d.doff + i;
+    for (int ax = 1; ax < d.nd; ax++) {
+        const int64_t j = o % d.dims[ax];
+        o /= d.dims[ax];
+        so += j * d.sstr[ax];
+        doo += j * d.dstr[ax];
+    }
+    const SV in = src[so];
+    SV out;
+#pragma unroll
+    for (int k = 0; k < V; k++) out.v[k] = in.v[k] * a;
+    dst[doo] = out;
+}
+
+template <typename S, int V>
+__global__ __launch_bounds__(256) void k_scale_linear(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, S a)
+{
+    scale_linear_body<S, V>(src_, dst_, d,
+                            (int64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
+}
+
+/* tile of the scaling transpose: SCALE_TILE_TJ elements along ta, and along
+ * axis 0 as many elements as give rows of SCALE_TILE_ROWB bytes — the f32
+ * shape of the converting tile, and for f64 the same bytes per row and per
+ * tile */
+#define SCALE_TILE_TJ 64
+#define SCALE_TILE_ROWB 512
+template <typename S> __host__ __device__ constexpr int scale_tile_ti(int nc)
+{
+    return SCALE_TILE_ROWB / (int)sizeof(S) / nc;
+}
+template <typename S> __host__ __device__ constexpr int scale_tile_pitch(int nc)
+{
+    /* in scalars: >= ti*nc and == nc modulo 32.  A 32-lane half then reads
+     * scalar indices congruent to 32 consecutive values: 32 banks of the
+     * 32-bank ds_read_b32 for f32 (cvt_tile_pitch), 32 bank PAIRS of the
+     * 64-bank ds_read_b64 for f64 */
+    return nc + ((scale_tile_ti<S>(nc) - 1) * nc + 31) / 32 * 32;
+}
+
+/* LDS-tiled transpose with scaling: the layout of cvt_tile_body with S in
+ * LDS; the multiply sits on the store side.  bid is the (entry-local) flat
+ * block id, already checked against the block count. */
+template <typename S, int NC>
+__device__ __forceinline__ void scale_tile_body(
+    S *tile, const void *__restrict__ src_, void *__restrict__ dst_,
+    const DescDev &d, int ta, int64_t ntile_i, int64_t ntile_j, int64_t bid,
+    S a)
+{
+    constexpr int TI = scale_tile_ti<S>(NC), TJ = SCALE_TILE_TJ, NR = 16;
+    constexpr int PITCH = scale_tile_pitch<S>(NC);
+    const S *__restrict__ src = (const S *)src_;
+    S *__restrict__ dst = (S *)dst_;
+
+    const int tx = threadIdx.x; /* 0..63 */
+    const int ty = threadIdx.y; /* 0..NR-1 */
+    const int64_t t_i = bid % ntile_i;
+    int64_t rest = bid / ntile_i;
+    const int64_t t_j = rest % ntile_j;
+    int64_t batch = rest / ntile_j;
+
+    int64_t so_b = d.soff, do_b = d.doff;
+    for (int ax = 1; ax < d.nd; ax++) {
+        if (ax == ta) continue;
+        const int64_t j = batch % d.dims[ax];
+        batch /= d.dims[ax];
+        so_b += j * d.sstr[ax];
+        do_b += j * d.dstr[ax];
+    }
+
+    const int64_t i0 = t_i * TI;
+    const int ni = (int)(d.dims[0] - i0 < TI ? d.dims[0] - i0 : TI);
+    const int64_t j0 = t_j * TJ;
+    const int nj = (int)(d.dims[ta] - j0 < TJ ? d.dims[ta] - j0 : TJ);
+
+    /* load: lanes sweep the scalars of one src row, rows sweep ta */
+    {
+        const int64_t sj = d.sstr[ta];
+        const S *base = src + (so_b + i0 + j0 * sj) * NC;
+        const int nw = ni * NC;
+        for (int j = ty; j < nj; j += NR) {
+            const S *row = base + (int64_t)j * sj * NC;
+            S *trow = tile + j * PITCH;
+            for (int q = tx; q < nw; q += 64) trow[q] = row[q];
+        }
+    }
+    __syncthreads();
+    /* store: lanes sweep the scalars of one dst row, rows sweep axis 0 */
+    {
+        const int64_t di = d.dstr[0];
+        S *base = dst + (do_b + j0 + i0 * di) * NC;
+        const int nw = nj * NC;
+        for (int i = ty; i < ni; i += NR) {
+            S *row = base + (int64_t)i * di * NC;
+            const S *tcol = tile + i * NC;
+            for (int q = tx; q < nw; q += 64) {
+                const int j = q / NC;
+                row[q] = tcol[q + j * (PITCH - NC)] * a;
+            }
+        }
+    }
+}
+
+template <typename S, int NC>
+__global__ __launch_bounds__(1024) void k_scale_tile(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int ta,
+    int64_t ntile_i, int64_t ntile_j, int64_t nblocks, S a)
+{
+    __shared__ S tile[SCALE_TILE_TJ * scale_tile_pitch<S>(NC)];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    scale_tile_body<S, NC>(tile, src_, dst_, d, ta, ntile_i, ntile_j, bid, a);
+}
+
+/* Grouped forms: one launch over the entries of one V resp. all tile entries
+ * of a stage, S and NC being plan constants and alpha a kernel argument, so
+ * the tables do not depend on it.  GEntry serves as is, njchunk carrying
+ * ntile_j. */
+template <typename S, int V>
+__global__ __launch_bounds__(256) void k_group_scale_linear(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks, S a)
+{
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    scale_linear_body<S, V>(g.src, g.dst, g.d, bid - first[e], a);
+}
+
+template <typename S, int NC>
+__global__ __launch_bounds__(1024) void k_group_scale_tile(
+    const int64_t *__restrict__ first, const GEntry *__restrict__ ent,
+    int nent, int64_t nblocks, S a)
+{
+    __shared__ S tile[SCALE_TILE_TJ * scale_tile_pitch<S>(NC)];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GEntry &g = ent[e];
+    scale_tile_body<S, NC>(tile, g.src, g.dst, g.d, g.ta, g.ntile_i,
+                           g.njchunk, bid - first[e], a);
+}
+
+/* Elementwise scaling fallback: descriptors with no contiguous axis, and
+ * transposable ones with more than 4 scalars per element. */
+template <typename S>
+__global__ __launch_bounds__(256) void k_scale_generic(
+    const void *__restrict__ src_, void *__restrict__ dst_, DescDev d, int nc,
+    S a)
+{
+    const S *__restrict__ src = (const S *)src_;
+    S *__restrict__ dst = (S *)dst_;
+    int64_t idx = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) *
+                      blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * gridDim.y * blockDim.x;
+    const int64_t nscal = d.total * nc;
+    for (; idx < nscal; idx += stride) {
+        int64_t rem = idx / nc;
+        const int64_t c = idx - rem * nc;
+        int64_t so = d.soff, doo = d.doff;
+        for (int ax = 0; ax < d.nd; ax++) {
+            const int64_t j = rem % d.dims[ax];
+            rem /= d.dims[ax];
+            so += j * d.sstr[ax];
+            doo += j * d.dstr[ax];
+        }
+        dst[doo * nc + c] = src[so * nc + c] * a;
+    }
+}
+
 /* ================= descriptor normalization & dispatch ============= */
 
 struct CopyDescH {
@@ -1646,6 +1839,7 @@ static pa_status launch_desc(const CopyDescH &dn, int64_t ssz, int64_t ncomp,
 struct CvtSel {
     int kind = PA_KERNEL_NONE;
     int wire = 0, op = 0, ncomp = 1;
+    int scalar = 0;     /* PA_KERNEL_SCALE_*: PA_SCALAR_*, wire = op = 0 */
     int V = 1;          /* scalars per access (linear) */
     int ti = 0, tj = 0; /* tile shape in elements (tile) */
     int ta = -1;        /* dst-contiguous axis (tile) */
@@ -1744,17 +1938,21 @@ static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
     return 0;
 }
 
-/* workgroups of a converting selection: the grid launch_cvt_sel() launches */
+/* workgroups of a converting or scaling selection: the grid launch_cvt_sel()
+ * resp. launch_scale_sel() launches */
 static int64_t cvt_grid(const CvtSel &k, int64_t *nti, int64_t *ntj)
 {
     const CopyDescH &w = k.d;
     *nti = *ntj = 0;
     switch (k.kind) {
     case PA_KERNEL_CVT_LINEAR:
+    case PA_KERNEL_SCALE_LINEAR:
         return grid_exact(w.total, 256);
     case PA_KERNEL_CVT_GENERIC:
+    case PA_KERNEL_SCALE_GENERIC:
         return grid_for(w.total * k.ncomp, 256);
-    case PA_KERNEL_CVT_TILE: {
+    case PA_KERNEL_CVT_TILE:
+    case PA_KERNEL_SCALE_TILE: {
         int64_t nbatch = 1;
         for (int a = 1; a < w.nd; a++)
             if (a != k.ta) nbatch *= w.dims[a];
@@ -1868,6 +2066,161 @@ static pa_status launch_desc_cvt(const CopyDescH &dn, int wire, int op,
     pa_status st = select_kernel_cvt(dn, wire, op, ncomp, src, dst, &k);
     if (st) return st;
     return launch_cvt_sel(k, src, dst, stream);
+}
+
+/* ---- scaled copies: selection and launch ------------------------------ */
+
+/* bytes of a PA_SCALAR_* code, 0 for an unknown one */
+static int64_t scalar_bytes(int scalar)
+{
+    return scalar == PA_SCALAR_F32 ? 4 : scalar == PA_SCALAR_F64 ? 8 : 0;
+}
+
+static pa_status check_scale(int scalar, int64_t nscal, double alpha)
+{
+    if (!scalar_bytes(scalar))
+        return fail("unknown scalar type %d (PA_SCALAR_F32 = 1, "
+                    "PA_SCALAR_F64 = 2)", scalar);
+    if (nscal < 1) return fail("invalid nscal %lld", (long long)nscal);
+    if (!std::isfinite(alpha)) return fail("scale alpha must be finite");
+    return 0;
+}
+
+/* The decision for a scaling copy, in ONE place: launch_scale_sel() executes
+ * it, pa_copy_kernel_kind_scale() reports it.  The rules are those of
+ * select_kernel_cvt() with one scalar type on both sides; the selection
+ * lives in a CvtSel (ncomp = scalars per element). */
+static pa_status select_kernel_scale(const CopyDescH &dn, int scalar,
+                                     int64_t nscal, const void *src,
+                                     const void *dst, CvtSel *out)
+{
+    if (pa_status st = check_scale(scalar, nscal, 0.0)) return st;
+    *out = CvtSel();
+    out->scalar = scalar;
+    out->ncomp = (int)nscal;
+    if (dn.total == 0) return 0;
+    const int64_t sz = scalar_bytes(scalar);
+
+    if (dn.sstr[0] == 1 && dn.dstr[0] == 1) {
+        /* scalar units: the components join the contiguous axis */
+        CopyDescH w = dn;
+        w.dims[0] *= nscal;
+        w.soff *= nscal;
+        w.doff *= nscal;
+        for (int a = 1; a < w.nd; a++) {
+            w.sstr[a] *= nscal;
+            w.dstr[a] *= nscal;
+        }
+        int64_t V = 16 / sz;
+        auto ok = [&](int64_t v) {
+            if (w.dims[0] % v || w.soff % v || w.doff % v) return false;
+            if ((uintptr_t)src % (uintptr_t)(v * sz)) return false;
+            if ((uintptr_t)dst % (uintptr_t)(v * sz)) return false;
+            for (int a = 1; a < w.nd; a++)
+                if (w.sstr[a] % v || w.dstr[a] % v) return false;
+            return true;
+        };
+        while (V > 1 && !ok(V)) V >>= 1;
+        w.dims[0] /= V;
+        w.soff /= V;
+        w.doff /= V;
+        for (int a = 1; a < w.nd; a++) {
+            w.sstr[a] /= V;
+            w.dstr[a] /= V;
+        }
+        w.total = 1;
+        for (int a = 0; a < w.nd; a++) w.total *= w.dims[a];
+        out->kind = PA_KERNEL_SCALE_LINEAR;
+        out->V = (int)V;
+        out->d = w;
+        return 0;
+    }
+
+    out->d = dn;
+    int ta = -1;
+    if (dn.sstr[0] == 1)
+        for (int a = 1; a < dn.nd; a++)
+            if (dn.dstr[a] == 1) { ta = a; break; }
+    if (ta > 0 && nscal <= PA_CVT_TILE_MAX_COMP) {
+        out->kind = PA_KERNEL_SCALE_TILE;
+        out->ta = ta;
+        out->ti = scalar == PA_SCALAR_F32 ? scale_tile_ti<float>((int)nscal)
+                                          : scale_tile_ti<double>((int)nscal);
+        out->tj = SCALE_TILE_TJ;
+        return 0;
+    }
+    out->kind = PA_KERNEL_SCALE_GENERIC;
+    return 0;
+}
+
+/* the single-descriptor launches of scalar type S; a = S(alpha) */
+template <typename S>
+static pa_status launch_scale_sel_t(const CvtSel &k, const void *src,
+                                    void *dst, S a, hipStream_t stream)
+{
+    int64_t nti, ntj;
+    const int64_t nblocks = cvt_grid(k, &nti, &ntj);
+    DescDev dd = to_dev(k.d);
+    dim3 grid;
+    switch (k.kind) {
+    case PA_KERNEL_SCALE_LINEAR: {
+        if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
+#define SCALE_LIN(V)                                                         \
+    hipLaunchKernelGGL((k_scale_linear<S, V>), grid, dim3(256), 0, stream,   \
+                       src, dst, dd, a)
+        /* V starts at 16 / sizeof(S): 4 only exists for f32 */
+        if (k.V != 1 && k.V != 2 && !(k.V == 4 && sizeof(S) == 4))
+            return fail("bad vector width %d", k.V);
+        if constexpr (sizeof(S) == 4) {
+            if (k.V == 4) SCALE_LIN(4);
+        }
+        if (k.V == 2)
+            SCALE_LIN(2);
+        else if (k.V == 1)
+            SCALE_LIN(1);
+#undef SCALE_LIN
+        break;
+    }
+    case PA_KERNEL_SCALE_TILE: {
+        if (k.ta < 1 || k.ncomp < 1 || k.ncomp > PA_CVT_TILE_MAX_COMP ||
+            k.ti != scale_tile_ti<S>(k.ncomp) || k.tj != SCALE_TILE_TJ)
+            return fail("bad scaling-tile selection");
+        if (pa_status gst = grid2d(nblocks, 64 * 16, &grid)) return gst;
+#define SCALE_TILE_NC(NC)                                                    \
+    hipLaunchKernelGGL((k_scale_tile<S, NC>), grid, dim3(64, 16), 0, stream, \
+                       src, dst, dd, k.ta, nti, ntj, nblocks, a)
+        if (k.ncomp == 1)
+            SCALE_TILE_NC(1);
+        else if (k.ncomp == 2)
+            SCALE_TILE_NC(2);
+        else if (k.ncomp == 3)
+            SCALE_TILE_NC(3);
+        else
+            SCALE_TILE_NC(4);
+#undef SCALE_TILE_NC
+        break;
+    }
+    case PA_KERNEL_SCALE_GENERIC:
+        grid = dim3((uint32_t)nblocks); /* grid-stride kernel */
+        hipLaunchKernelGGL((k_scale_generic<S>), grid, dim3(256), 0, stream,
+                           src, dst, dd, k.ncomp, a);
+        break;
+    default:
+        return fail("bad scaling kernel kind %d", k.kind);
+    }
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static pa_status launch_scale_sel(const CvtSel &k, const void *src, void *dst,
+                                  double alpha, hipStream_t stream)
+{
+    if (k.kind == PA_KERNEL_NONE) return 0;
+    if (k.scalar == PA_SCALAR_F32)
+        return launch_scale_sel_t<float>(k, src, dst, (float)alpha, stream);
+    if (k.scalar == PA_SCALAR_F64)
+        return launch_scale_sel_t<double>(k, src, dst, alpha, stream);
+    return fail("bad scalar type %d", k.scalar);
 }
 
 /* ---- zero fill: descriptor, store width, launch ----------------------- */
@@ -2082,6 +2435,13 @@ struct pa_plan {
     /* PA_PLAN_GROUP_CVT was given: on a wire plan the converting entries of
      * a stage share grouped launches (build_stage); no effect otherwise */
     bool group_cvt = false;
+    /* scaled transpose (pa_plan_set_scale): the PA_SCALAR_* code, or 0 for a
+     * plan without a scale; an element is nscal such scalars.  The local
+     * copy, the self unpack and the unpacks multiply by alpha, which is a
+     * kernel argument and not part of the stage tables. */
+    int scale = 0;
+    int64_t nscal = 1;
+    double alpha = 1.0;
     int R;    /* -1 = same decomposition */
     int P;    /* subgroup size */
     int myk;  /* my coordinate along R */
@@ -2921,6 +3281,36 @@ int pa_plan_group_cvt(const pa_plan *p)
     return p && p->wire && p->group_cvt ? 1 : 0;
 }
 
+pa_status pa_plan_set_scale(pa_plan *p, int scalar, double alpha)
+{
+    if (!p) return fail("null plan");
+    if (p->wire)
+        return fail("a plan with a wire pair takes no scale: that would be "
+                    "two roundings per element");
+    if (pa_status st = check_scale(scalar, 1, alpha)) return st;
+    const int64_t sz = scalar_bytes(scalar);
+    if (p->esz % sz)
+        return fail("element size %lld is not a multiple of the %lld-byte "
+                    "scalar", (long long)p->esz, (long long)sz);
+    /* alpha == 1 is "no scale": the plan runs what it runs without one */
+    const int scale = alpha == 1.0 ? 0 : scalar;
+    /* the tables hold the kernel selection, not alpha: they survive a change
+     * of alpha and go when the selection changes */
+    if (scale != p->scale) free_stage_tables(p);
+    p->scale = scale;
+    p->nscal = scale ? p->esz / sz : 1;
+    p->alpha = scale ? alpha : 1.0;
+    return 0;
+}
+
+int pa_plan_scale(const pa_plan *p, int *scalar, double *alpha)
+{
+    if (!p || !p->scale) return 0;
+    if (scalar) *scalar = p->scale;
+    if (alpha) *alpha = p->alpha;
+    return 1;
+}
+
 pa_status pa_plan_create_keep(const pa_pencil *pin, const pa_pencil *pout,
                               int64_t scalar_size, int64_t ncomp, int e,
                               const int64_t *extra_dims, int rank, int flags,
@@ -3021,8 +3411,9 @@ pa_status pa_transpose_execute(pa_plan *p, const void *src_parent,
 
     /* a keep plan runs the n = 1 stage path: pack -> exchange -> local +
      * fill -> unpack (the fallback above is sized in kept elements); so does
-     * a wire plan with grouped converting kernels (sized in wire bytes) */
-    if (p->keep || pa_plan_group_cvt(p)) {
+     * a wire plan with grouped converting kernels (sized in wire bytes) and
+     * a scaled plan, whose scaling kernels are grouped from the start */
+    if (p->keep || pa_plan_group_cvt(p) || p->scale) {
         const void *srcs[1] = {src_parent};
         void *dsts[1] = {dst_parent};
         return pa_transpose_execute_many(p, 1, srcs, dsts, stream_);
@@ -3334,6 +3725,42 @@ pa_status pa_copy_kernel_kind_wire(int nd, const int64_t *dims,
     return 0;
 }
 
+pa_status pa_device_copy_scale(int nd, const int64_t *dims,
+                               const int64_t *sstr, int64_t soff,
+                               const int64_t *dstr, int64_t doff, int scalar,
+                               int64_t nscal, double alpha, const void *src,
+                               void *dst, void *stream)
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_scale(scalar, nscal, alpha)) return st;
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    CvtSel k;
+    if (pa_status st = select_kernel_scale(d, scalar, nscal, src, dst, &k))
+        return st;
+    return launch_scale_sel(k, src, dst, alpha, (hipStream_t)stream);
+}
+
+pa_status pa_copy_kernel_kind_scale(int nd, const int64_t *dims,
+                                    const int64_t *sstr, int64_t soff,
+                                    const int64_t *dstr, int64_t doff,
+                                    int scalar, int64_t nscal,
+                                    const void *src, const void *dst,
+                                    int64_t out[5])
+{
+    if (!out) return fail("null output");
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    CvtSel k;
+    if (pa_status st = select_kernel_scale(d, scalar, nscal, src, dst, &k))
+        return st;
+    out[0] = k.kind;
+    out[1] = k.V;
+    out[2] = k.ti;
+    out[3] = k.tj;
+    out[4] = 1; /* the scaling tile sweeps one tile per workgroup */
+    return 0;
+}
+
 } /* extern "C" */
 
 /* ================= multi-field transposes ========================== */
@@ -3354,7 +3781,8 @@ enum {
 
 struct StageItem {
     KernelSel k;
-    bool cvt = false; /* wire plan: the converting selection c runs, not k */
+    bool cvt = false; /* wire plan, or a scaled plan's destination side: the
+                       * converting / scaling selection c runs, not k */
     CvtSel c;
     bool fill = false; /* keep plan: a zero-fill entry, fs instead of k */
     FillSel fs;
@@ -3453,24 +3881,34 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         StageItem it;
         it.src = src;
         it.dst = dst;
-        if (p->wire) {
+        /* a scaled plan multiplies on the destination side only: the local
+         * copy, the self unpack and the unpacks; its packs stay ordinary */
+        const bool scaled = p->scale && (which == 0 || which == 2 || which == 4);
+        if (p->wire || scaled) {
             /* converting kernels: ungrouped rows, one launch per entry,
              * unless the plan asks for grouped ones */
-            const int op = which == 0 ? PA_WIRE_ROUND
+            const int op = scaled       ? 0
+                           : which == 0 ? PA_WIRE_ROUND
                            : (which == 1 || which == 3) ? PA_WIRE_NARROW
                                                         : PA_WIRE_WIDEN;
             it.cvt = true;
-            if (pa_status st = select_kernel_cvt(d, p->wire, op, p->ncomp,
-                                                 src, dst, &it.c))
+            if (pa_status st =
+                    scaled ? select_kernel_scale(d, p->scale, p->nscal, src,
+                                                 dst, &it.c)
+                           : select_kernel_cvt(d, p->wire, op, p->ncomp, src,
+                                               dst, &it.c))
                 return st;
             it.nblocks = cvt_grid(it.c, &it.nti, &it.njc);
             if (it.nblocks == 0) return 0;
             /* PA_PLAN_GROUP_CVT: linear entries of one (op, V) and tile
-             * entries of one op share a grouped launch */
-            const bool grp = p->group_cvt &&
-                             (it.c.kind == PA_KERNEL_CVT_LINEAR ||
-                              it.c.kind == PA_KERNEL_CVT_TILE);
-            const int vec = it.c.kind == PA_KERNEL_CVT_LINEAR ? it.c.V : 0;
+             * entries of one op share a grouped launch; the scaling kernels
+             * are grouped the same way without a flag */
+            const bool lin = it.c.kind == PA_KERNEL_CVT_LINEAR ||
+                             it.c.kind == PA_KERNEL_SCALE_LINEAR;
+            const bool grp = (scaled || p->group_cvt) &&
+                             (lin || it.c.kind == PA_KERNEL_CVT_TILE ||
+                              it.c.kind == PA_KERNEL_SCALE_TILE);
+            const int vec = lin ? it.c.V : 0;
             const int idx = (int)t->items.size();
             t->items.push_back(it);
             if (grp)
@@ -3676,6 +4114,42 @@ static void launch_group_cvt(const StageLaunch &l, int ncomp, dim3 grid,
 #undef GROUP_CVT
 }
 
+/* the grouped scaling launch of scalar type S: V resp. the scalars per
+ * element pick the instance, as in launch_scale_sel_t() */
+template <typename S>
+static pa_status launch_group_scale(const StageLaunch &l, int nscal,
+                                    dim3 grid, hipStream_t stream,
+                                    const int64_t *first, const GEntry *ent,
+                                    int ne, S a)
+{
+#define GROUP_SCALE(kern, block)                                             \
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
+                       l.nblocks, a)
+    if (l.kind == PA_KERNEL_SCALE_LINEAR) {
+        if (l.vec != 1 && l.vec != 2 && !(l.vec == 4 && sizeof(S) == 4))
+            return fail("bad grouped scaling launch");
+        if constexpr (sizeof(S) == 4) {
+            if (l.vec == 4)
+                GROUP_SCALE((k_group_scale_linear<S, 4>), dim3(256));
+        }
+        if (l.vec == 2)
+            GROUP_SCALE((k_group_scale_linear<S, 2>), dim3(256));
+        else if (l.vec == 1)
+            GROUP_SCALE((k_group_scale_linear<S, 1>), dim3(256));
+    } else if (nscal == 1)
+        GROUP_SCALE((k_group_scale_tile<S, 1>), dim3(64, 16));
+    else if (nscal == 2)
+        GROUP_SCALE((k_group_scale_tile<S, 2>), dim3(64, 16));
+    else if (nscal == 3)
+        GROUP_SCALE((k_group_scale_tile<S, 3>), dim3(64, 16));
+    else if (nscal == 4)
+        GROUP_SCALE((k_group_scale_tile<S, 4>), dim3(64, 16));
+    else
+        return fail("bad grouped scaling launch");
+#undef GROUP_SCALE
+    return 0;
+}
+
 static pa_status launch_group(const pa_plan *p, const StageLaunch &l,
                               hipStream_t stream)
 {
@@ -3706,6 +4180,23 @@ static pa_status launch_group(const pa_plan *p, const StageLaunch &l,
     launch_group_cvt<W, O>(l, (int)p->ncomp, grid, stream, first, ent, ne)
         CVT_FOR_WIRE_OP(p->wire, l.op, GROUP_CVT_WO)
 #undef GROUP_CVT_WO
+        HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    if (l.kind == PA_KERNEL_SCALE_LINEAR || l.kind == PA_KERNEL_SCALE_TILE) {
+        const bool lin = l.kind == PA_KERNEL_SCALE_LINEAR;
+        if (pa_status gst = grid2d(l.nblocks, lin ? 256 : 64 * 16, &grid))
+            return gst;
+        pa_status st;
+        if (p->scale == PA_SCALAR_F32)
+            st = launch_group_scale<float>(l, (int)p->nscal, grid, stream,
+                                           first, ent, ne, (float)p->alpha);
+        else if (p->scale == PA_SCALAR_F64)
+            st = launch_group_scale<double>(l, (int)p->nscal, grid, stream,
+                                            first, ent, ne, p->alpha);
+        else
+            st = fail("grouped scaling launch on a plan without a scale");
+        if (st) return st;
         HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -3788,7 +4279,8 @@ static pa_status many_check(const pa_plan *p, int n, int stage,
         for (int f = 0; f < n; f++)
             if (!dsts[f]) return fail("null dst pointer for field %d", f);
     }
-    if (p->own_bufs && !((p->keep || pa_plan_group_cvt(p)) && n == 1))
+    if (p->own_bufs &&
+        !((p->keep || pa_plan_group_cvt(p) || p->scale) && n == 1))
         return fail("multi-field stages need staging buffers of "
                     "pa_plan_buffer_sizes_many bytes from pa_plan_set_buffers");
     if ((p->send_total > 0 && !p->send_buf) ||
@@ -3832,8 +4324,10 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
             st = launch_group(p, l, stream);
         else {
             const StageItem &it = t->items[l.items[0]];
-            st = it.cvt ? launch_cvt_sel(it.c, it.src, it.dst, stream)
-                        : launch_sel(it.k, it.src, it.dst, stream);
+            st = !it.cvt ? launch_sel(it.k, it.src, it.dst, stream)
+                 : it.c.scalar
+                     ? launch_scale_sel(it.c, it.src, it.dst, p->alpha, stream)
+                     : launch_cvt_sel(it.c, it.src, it.dst, stream);
         }
         if (st) return st;
     }

@@ -71,6 +71,13 @@ KERNEL_CVT_GENERIC = 11
 # grouped zero fill of a truncated transpose (pa_fill_kernel_kind)
 KERNEL_FILL = 12
 FILL_NONE, FILL_ZERO = 0, 1
+# scaling kernels of a scaled transpose (pa_copy_kernel_kind_scale)
+KERNEL_SCALE_LINEAR = 13
+KERNEL_SCALE_TILE = 14
+KERNEL_SCALE_GENERIC = 15
+# real scalar types of a scale (pa_plan_set_scale)
+SCALAR_F32, SCALAR_F64 = 1, 2
+SCALAR_BYTES = {SCALAR_F32: 4, SCALAR_F64: 8}
 KERNEL_NAMES = {
     KERNEL_NONE: "NONE", KERNEL_COPY_1D: "COPY_1D",
     KERNEL_COPY_1D_NT: "COPY_1D_NT", KERNEL_LINEAR: "LINEAR",
@@ -78,7 +85,8 @@ KERNEL_NAMES = {
     KERNEL_TILE_PK: "TILE_PK", KERNEL_GENERIC: "GENERIC",
     KERNEL_TILE_WIDE: "TILE_WIDE", KERNEL_CVT_LINEAR: "CVT_LINEAR",
     KERNEL_CVT_TILE: "CVT_TILE", KERNEL_CVT_GENERIC: "CVT_GENERIC",
-    KERNEL_FILL: "FILL",
+    KERNEL_FILL: "FILL", KERNEL_SCALE_LINEAR: "SCALE_LINEAR",
+    KERNEL_SCALE_TILE: "SCALE_TILE", KERNEL_SCALE_GENERIC: "SCALE_GENERIC",
 }
 
 # wire pairs (stored -> wire) and ops of a converting copy
@@ -205,6 +213,38 @@ def device_copy_wire(desc, wire: int, op: int, ncomp: int, src_ptr: int,
         nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
         (I64 * nd)(*dstr), I64(doff), int(wire), int(op), I64(ncomp),
         VP(src_ptr), VP(dst_ptr), VP(stream)), "pa_device_copy_wire")
+
+
+def copy_kernel_kind_scale(desc, scalar: int, nscal: int = 1,
+                           src_ptr: int = 0,
+                           dst_ptr: int = 0) -> WireKernelKind:
+    """Which scaling kernel ``pa_device_copy_scale`` / a scaled plan launches
+    for ``desc`` (element units, ``nscal`` scalars of type ``scalar`` per
+    element); host-only, the pointers are used for their alignment only.
+    The fields are those of :func:`copy_kernel_kind_wire`."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    out = (I64 * 5)()
+    _check(lib, lib.pa_copy_kernel_kind_scale(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), int(scalar), I64(nscal),
+        VP(src_ptr), VP(dst_ptr), out), "pa_copy_kernel_kind_scale")
+    return WireKernelKind(*(int(v) for v in out))
+
+
+def device_copy_scale(desc, scalar: int, nscal: int, alpha: float,
+                      src_ptr: int, dst_ptr: int, stream: int = 0) -> None:
+    """Run one scaling strided copy on the device (pa_device_copy_scale):
+    ``dst = src * S(alpha)`` per real scalar."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    _check(lib, lib.pa_device_copy_scale(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), int(scalar), I64(nscal),
+        ctypes.c_double(alpha), VP(src_ptr), VP(dst_ptr), VP(stream)),
+        "pa_device_copy_scale")
 
 
 class FillKernelKind(NamedTuple):
@@ -344,6 +384,23 @@ class NativePlan:
         """True on a wire plan created with ``group_cvt=True``
         (pa_plan_group_cvt)."""
         return bool(self.lib.pa_plan_group_cvt(self._plan))
+
+    def set_scale(self, scalar: int, alpha: float):
+        """Make this a scaled plan, ``dest = alpha * T(src)`` per real scalar
+        of type ``scalar`` (SCALAR_F32 / SCALAR_F64); ``alpha == 1.0`` takes
+        the scale off again (pa_plan_set_scale)."""
+        _check(self.lib, self.lib.pa_plan_set_scale(
+            self._plan, int(scalar), ctypes.c_double(alpha)),
+            "pa_plan_set_scale")
+
+    def plan_scale(self):
+        """``(scalar, alpha)`` of a scaled plan (pa_plan_scale), else
+        None."""
+        sc, al = ctypes.c_int(), ctypes.c_double()
+        if not self.lib.pa_plan_scale(self._plan, ctypes.byref(sc),
+                                      ctypes.byref(al)):
+            return None
+        return int(sc.value), float(al.value)
 
     def buffer_sizes(self) -> Tuple[int, int]:
         s, r = I64(), I64()
@@ -728,15 +785,21 @@ def staging_pool(device) -> StagingPool:
     return _POOLS[idx]
 
 
-def _native_plan_for(plan, src, pair, group_cvt: bool = False) -> NativePlan:
+def _native_plan_for(plan, src, pair, group_cvt: bool = False,
+                     scale=None) -> NativePlan:
     """The native plan of a (Multi)Transposition over arrays like ``src``;
     ``pair`` is its wire.WirePair or None, ``group_cvt`` its
-    ``wire_grouped``."""
+    ``wire_grouped``, ``scale`` its scale.Scale or None."""
     if pair is None:
-        return NativePlan(plan.Pi, plan.Po, plan.rank,
-                          src.data.element_size(), plan.extra_dims,
-                          aliased=plan.aliased, ncomp=src.ncomp,
-                          keep=plan.keep, fill=plan.fill)
+        np_ = NativePlan(plan.Pi, plan.Po, plan.rank,
+                         src.data.element_size(), plan.extra_dims,
+                         aliased=plan.aliased, ncomp=src.ncomp,
+                         keep=plan.keep, fill=plan.fill)
+        if scale is not None:
+            np_.set_scale(scale.code, scale.alpha)
+        return np_
+    if scale is not None:
+        raise ValueError("scale together with a wire pair is not supported")
     return NativePlan(plan.Pi, plan.Po, plan.rank, pair.stored.itemsize,
                       plan.extra_dims, aliased=plan.aliased,
                       ncomp=src.ncomp * pair.comps, wire=pair.code,
@@ -754,7 +817,8 @@ class NativeTransposition:
         src = t.src
         self.np_plan = plan
         self.native = _native_plan_for(plan, src, getattr(t, "wire", None),
-                                       getattr(t, "wire_grouped", False))
+                                       getattr(t, "wire_grouped", False),
+                                       getattr(t, "scale", None))
         sb, rb = self.native.buffer_sizes()
         dev = src.data.device
         # Staging comes from the per-device shared pool (the reference's
@@ -813,7 +877,8 @@ class NativeMultiTransposition:
         src = mt.srcs[0]
         self.n = len(mt.srcs)
         self.native = _native_plan_for(plan, src, getattr(mt, "wire", None),
-                                       getattr(mt, "wire_grouped", False))
+                                       getattr(mt, "wire_grouped", False),
+                                       getattr(mt, "scale", None))
         sb, rb = self.native.buffer_sizes_many(self.n)
         dev = src.data.device
         self._need = (max(sb, 1), max(rb, 1))

@@ -30,6 +30,7 @@ from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
                    peer_message, stage_descs)
 from .plan import fourier_keep  # noqa: F401  (the keep-set helper, re-exported)
+from .scale import resolve_scale
 from .wire import narrow, resolve_wire, widen
 
 MPI_TAG = 42  # Transpositions.jl:469
@@ -62,6 +63,23 @@ def _check_keep_wire(keep, wire_dtype):
             "transpose moves the stored type")
 
 
+def _scale_of(dest: PencilArray, src: PencilArray, scale, wire_dtype):
+    """The scale.Scale of a transpose ``dest <- scale * src`` (ValueError for
+    a dtype or value the engine refuses, or together with a wire), or None
+    for no scale."""
+    if scale is None:
+        return None
+    if wire_dtype is not None:
+        raise ValueError(
+            "scale together with wire_dtype is not supported: that would be "
+            "two roundings per element")
+    if str(dest.data.dtype) != str(src.data.dtype):
+        raise ValueError(
+            f"a scaled transpose needs dest and src of one dtype: "
+            f"{dest.data.dtype} != {src.data.dtype}")
+    return resolve_scale(src.data.dtype, scale)
+
+
 def _check_wire_grouped(wire_grouped, wire_dtype):
     if wire_grouped and wire_dtype is None:
         raise ValueError(
@@ -79,7 +97,21 @@ class _Codec(NamedTuple):
     copy: Callable        # (which, desc, src, dst): run one descriptor
 
 
-def _codec(src: PencilArray, pair) -> _Codec:
+def _codec(src: PencilArray, pair, scale=None) -> _Codec:
+    if scale is not None:
+        # scaled: typed real scalars; the local copy, the self unpack and
+        # the unpacks multiply, the packs move the scalars as they are
+        nc = src.ncomp * scale.comps  # real scalars per element
+        a = scale.a
+
+        def mul(x):
+            with np.errstate(all="ignore"):
+                return x * a
+
+        conv = {0: mul, 1: lambda x: x, 2: mul, 3: lambda x: x, 4: mul}
+        return _Codec(lambda arr: arr.data.view(scale.real), None, nc,
+                      lambda which, d, s, t: apply_copy_conv(d, s, t, nc,
+                                                             conv[which]))
     if pair is None:
         # plain elements: one opaque item per element (vector-valued ones
         # included), so the element-unit descriptors apply unchanged
@@ -138,8 +170,17 @@ def _arrays_alias(a, b) -> bool:
 class Transposition:
     def __init__(self, dest: PencilArray, src: PencilArray,
                  method: str = "grouped", wire_dtype=None, keep=None,
-                 fill="zero", wire_grouped: bool = False):
+                 fill="zero", wire_grouped: bool = False, scale=None):
         """``Transposition(Ao, Ai; method)`` (Transpositions.jl:94-119).
+
+        ``scale`` (a finite real number) makes this a scaled transpose,
+        ``dest = scale * T(src)``: every real scalar of float32 / float64 /
+        complex64 / complex128 arrays (a complex item component by component)
+        is multiplied once by ``scale`` rounded to the scalar type, in the
+        pass that writes ``dest`` -- the local copy and the unpacks; messages
+        carry unscaled bytes (pa_plan_set_scale).  The normalisation of an
+        inverse FFT without a pass of its own.  ``None`` and ``1.0`` mean no
+        scale.  Works with ``keep``; not available with ``wire_dtype``.
 
         ``keep`` (``(a, b)`` per logical dim, ``None`` entries meaning full;
         see :func:`fourier_keep`) makes this a truncated transpose: only
@@ -184,6 +225,7 @@ class Transposition:
         self.method = method
         self.wire = _wire_pair(dest, src, wire_dtype)
         self.wire_grouped = bool(wire_grouped)
+        self.scale = _scale_of(dest, src, scale, wire_dtype)
         self.src = src
         self.dest = dest
         self.aliased = _arrays_alias(src.data, dest.data)
@@ -201,7 +243,7 @@ class Transposition:
         sub-block, one message per peer of the elements that move, the zero
         fill of a keep plan next to the local copy."""
         plan = self.plan
-        codec = _codec(self.src, self.wire)
+        codec = _codec(self.src, self.wire, self.scale)
         src, dst = codec.view(self.src), codec.view(self.dest)
         dt, sc = codec.carrier or src.dtype, codec.scale
         send_buf = np.empty(plan.send_nelem_total * sc, dtype=dt)
@@ -236,8 +278,8 @@ class Transposition:
         # 3. fused local (self) block overlaps the exchange (:394-404 + :530)
         for which, d in stage_descs(plan, 1, 0, 1):
             codec.copy(which, d, src if which == 0 else recv_buf, dst)
-        for fd in plan.fills:
-            apply_fill(fd, dst)
+        for fd in plan.fills:  # element units, whatever the codec's view
+            apply_fill(fd, self.dest.element_view())
         for r in reqs:
             r.wait()
 
@@ -285,14 +327,15 @@ class Transposition:
 
 def transpose_into(dest: PencilArray, src: PencilArray,
                    method: str = "grouped", wire_dtype=None, keep=None,
-                   fill="zero", wire_grouped: bool = False) -> PencilArray:
+                   fill="zero", wire_grouped: bool = False,
+                   scale=None) -> PencilArray:
     """``transpose!(dest, src; method)`` (Transpositions.jl:161-169)."""
     _check_wire_grouped(wire_grouped, wire_dtype)
     if dest is src:
         return dest
     return Transposition(dest, src, method=method, wire_dtype=wire_dtype,
-                         keep=keep, fill=fill,
-                         wire_grouped=wire_grouped).execute()
+                         keep=keep, fill=fill, wire_grouped=wire_grouped,
+                         scale=scale).execute()
 
 
 class MultiTransposition:
@@ -315,11 +358,12 @@ class MultiTransposition:
     ``wire_dtype``: a reduced-precision wire for every field, as in
     :class:`Transposition`; ``wire_grouped``: its converting kernels as
     grouped launches, likewise.  ``keep`` / ``fill``: a truncated transpose of
-    every field, as in :class:`Transposition`."""
+    every field, as in :class:`Transposition`.  ``scale``: one factor for
+    every field, likewise."""
 
     def __init__(self, dests: Sequence[PencilArray],
                  srcs: Sequence[PencilArray], wire_dtype=None, keep=None,
-                 fill="zero", wire_grouped: bool = False):
+                 fill="zero", wire_grouped: bool = False, scale=None):
         _check_keep_wire(keep, wire_dtype)
         _check_wire_grouped(wire_grouped, wire_dtype)
         dests, srcs = list(dests), list(srcs)
@@ -373,6 +417,7 @@ class MultiTransposition:
         self.wire_grouped = bool(wire_grouped)
         self.keep, self.fill = keep, fill
         self.wire = _wire_pair(d0, s0, wire_dtype)
+        self.scale = _scale_of(d0, s0, scale, wire_dtype)
         self.aliased = any(_arrays_alias(s.data, d.data)
                            for s in srcs for d in dests)
         self.plan: TransposePlan = build_plan(
@@ -391,8 +436,8 @@ class MultiTransposition:
             srcs = self.srcs
         for d, s in zip(self.dests, srcs):
             Transposition(d, s, wire_dtype=self.wire_dtype, keep=self.keep,
-                          fill=self.fill,
-                          wire_grouped=self.wire_grouped).execute()
+                          fill=self.fill, wire_grouped=self.wire_grouped,
+                          scale=self.scale and self.scale.alpha).execute()
 
     def execute(self, sync: bool = True):
         """Run the transposes; ``sync=False`` returns with the work enqueued
@@ -422,10 +467,12 @@ class MultiTransposition:
 
 def transpose_many_into(dests: Sequence[PencilArray],
                         srcs: Sequence[PencilArray], wire_dtype=None,
-                        keep=None, fill="zero", wire_grouped: bool = False):
+                        keep=None, fill="zero", wire_grouped: bool = False,
+                        scale=None):
     """``transpose!`` of every pair ``dests[i] <- srcs[i]`` in one call."""
     return MultiTransposition(dests, srcs, wire_dtype=wire_dtype, keep=keep,
-                              fill=fill, wire_grouped=wire_grouped).execute()
+                              fill=fill, wire_grouped=wire_grouped,
+                              scale=scale).execute()
 
 
 # ----------------------------------------------------------------------
@@ -437,19 +484,21 @@ def transpose_many_into(dests: Sequence[PencilArray],
 def run_transpose_sim(dests: Sequence[PencilArray],
                       srcs: Sequence[PencilArray],
                       staging_out=None, wire_dtype=None, keep=None,
-                      fill="zero", wire_grouped: bool = False) -> None:
+                      fill="zero", wire_grouped: bool = False,
+                      scale=None) -> None:
     """:func:`run_transpose_sim_many` with one field per rank (``n = 1`` is
     the single-field staging layout): ``dests[r] <- srcs[r]``."""
     return run_transpose_sim_many([[d] for d in dests], [[s] for s in srcs],
                                   staging_out, wire_dtype=wire_dtype,
                                   keep=keep, fill=fill,
-                                  wire_grouped=wire_grouped)
+                                  wire_grouped=wire_grouped, scale=scale)
 
 
 def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
                            staging_out=None, wire_dtype=None, keep=None,
-                           fill="zero", wire_grouped: bool = False) -> None:
+                           fill="zero", wire_grouped: bool = False,
+                           scale=None) -> None:
     """Every rank's transpose of ``n`` fields with the multi-field staging
     layout (plan.py): every field of a rank is packed into ONE n-fold send
     buffer, and the exchange is ONE slice copy per peer pair of ``n * c``
@@ -463,7 +512,10 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
     ``keep`` / ``fill``: a truncated transpose; the staging buffers then hold
     the kept elements only, a peer pair with nothing kept copies nothing, and
     every field gets the zero fill.  ``wire_grouped`` is accepted for parity
-    with :class:`Transposition`: the host mirror has no launches to group."""
+    with :class:`Transposition`: the host mirror has no launches to group.
+    ``scale``: a scaled transpose; the staging buffers then hold the real
+    scalars of the unscaled elements, byte for byte those of the run without
+    a scale, and the local copy and the unpacks multiply."""
     _check_keep_wire(keep, wire_dtype)
     _check_wire_grouped(wire_grouped, wire_dtype)
     nranks = len(srcs_per_rank)
@@ -472,7 +524,8 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
             any(len(x) != n for x in dests_per_rank):
         raise ValueError("every rank needs the same number (>= 1) of fields")
     s00, d00 = srcs_per_rank[0][0], dests_per_rank[0][0]
-    codec = _codec(s00, _wire_pair(d00, s00, wire_dtype))
+    codec = _codec(s00, _wire_pair(d00, s00, wire_dtype),
+                   _scale_of(d00, s00, scale, wire_dtype))
     plans = []
     for r in range(nranks):
         s0, d0 = srcs_per_rank[r][0], dests_per_rank[r][0]
@@ -506,8 +559,8 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
                 codec.copy(which, d,
                            sflat[r][f] if which == 0 else recv_bufs[r],
                            dflat[r][f])
-            for fd in p.fills:
-                apply_fill(fd, dflat[r][f])
+            for fd in p.fills:  # element units, whatever the codec's view
+                apply_fill(fd, dests_per_rank[r][f].element_view())
 
     # exchange: ONE slice copy per peer pair, all n fields in it
     for r, p in enumerate(plans):
