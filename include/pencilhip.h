@@ -500,6 +500,29 @@ pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
                                    const void *src, const void *dst,
                                    int64_t out[5]);
 
+/* Cache policy of the kernel pa_device_copy, or an ungrouped plan entry,
+ * launches for this descriptor (host-only, arguments of pa_copy_kernel_kind).
+ * *out = 1: the streaming form of PA_KERNEL_TILE_VS, nontemporal loads and
+ * nontemporal 16-byte vector stores (the two are one policy: the probe behind
+ * it, profiles/stream_tile_probe.txt, shows neither paying alone); chosen
+ * when the descriptor moves at least the stream threshold in bytes, one
+ * direction.  *out = 0: plain accesses, always so for every other kind.  The
+ * kind, word, byteified flag and sweep depth of pa_copy_kernel_kind do not
+ * depend on it, and the bytes written are the same either way.  Grouped
+ * launches of a multi-field stage (pa_transpose_*_many, entries of sweep
+ * depth 1) keep plain accesses. */
+pa_status pa_copy_kernel_stream(int nd, const int64_t *dims,
+                                const int64_t *sstr, int64_t soff,
+                                const int64_t *dstr, int64_t doff,
+                                int64_t elem_size, const void *src,
+                                const void *dst, int64_t *out);
+/* Set the stream threshold in payload bytes and return the previous one
+ * (default 512 MiB).  0 = stream wherever the vector-store tile runs,
+ * negative = never.  A tuning and testing hook: process-wide, read when a
+ * kernel is selected, so stage tables a plan has already built keep the
+ * policy they were built with. */
+int64_t pa_set_stream_min_bytes(int64_t min_bytes);
+
 /* ---- converting copies (reduced-precision wire) ------------------------ */
 /* One strided-copy descriptor with conversion (the kernels a wire plan
  * uses).  Strides, offsets and dims in ELEMENTS of ncomp scalars, components

@@ -37,6 +37,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -266,6 +267,19 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
                                                 ntile_i, njchunk, bid);
 }
 
+/* The 16-B store of the vector-store tile under its cache policy: plain, or
+ * nontemporal (STREAM, see tile_vs_body). */
+template <bool STREAM>
+__device__ __forceinline__ void vs_store16(void *p, uint4 q)
+{
+    if (STREAM) {
+        v4u_nt v = {q.x, q.y, q.z, q.w};
+        __builtin_nontemporal_store(v, (v4u_nt *)p);
+    } else {
+        *(uint4 *)p = q;
+    }
+}
+
 /* LDS-tiled transpose with VECTOR (16-B) STORES: 64(i) x 128(j) tile, each
  * lane storing a j-pair as one uint4 — 1024-B write bursts per instruction.
  * Interleaved-median probe (profiles/r2_probe_kernels*.txt): +1.5-1.8% over
@@ -275,8 +289,25 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile(
  * (except the unit ta axis) and the dst offset are EVEN and the dst base
  * pointer is 16-B aligned, so every vector store is aligned.  Tail j-tiles
  * (nj < TJ or odd) take a scalar epilogue.  Body shared with the grouped
- * k_group_tile_vs, like tile_body. */
-template <typename T, int TI, int TJ, int NROWS, int JCHUNK>
+ * k_group_tile_vs, like tile_body.
+ *
+ * STREAM: nontemporal loads AND nontemporal 16-B vector stores, for payloads
+ * far past the caches (select_kernel() gates on payload bytes, like
+ * k_copy_1d_nt).  Cache-policy probe at the headline shape, 24 interleaved
+ * rounds (tools/probe_stream_tile.hip, profiles/stream_tile_probe.txt): plain
+ * 5737 GB/s median, nt stores alone 5842, nt loads alone 5558 (a loss), both
+ * 5938 (min 5880 above the control's max 5814).  Write-through (sc1, sc0 sc1)
+ * stores measured no better than nt (5837 / 5821 alone, 5908 / 5909 with nt
+ * loads) and did not lift the one-direction write-pattern ceiling, and a
+ * strided sweep lost 3-5% under every policy, so neither is in the kernel.
+ * The two axes travel as ONE policy because neither holds alone: nt loads
+ * alone lose at the headline shape and nt stores alone lose at 2 GiB.  On the
+ * benchmark's headline the stores alone add 22 GiB/s and the loads 9 more,
+ * each above the parent's run-to-run spread of 5 (profiles/
+ * stream_tile_bench.txt).  The odd-tail and partial-tile scalar stores stay
+ * plain. */
+template <typename T, int TI, int TJ, int NROWS, int JCHUNK,
+          bool STREAM = false>
 __device__ __forceinline__ void tile_vs_body(
     T (&tile)[TI][TJ + 2], const T *__restrict__ src, T *__restrict__ dst,
     const DescDev &d, int ta, int64_t ntile_i, int64_t njchunk, int64_t bid)
@@ -312,7 +343,9 @@ __device__ __forceinline__ void tile_vs_body(
             for (int j = ty; j < nj; j += NROWS) {
                 const int64_t row = base + (int64_t)j * d.sstr[ta];
                 for (int i = tx; i < ni; i += 64)
-                    tile[i][j] = src[row + i];
+                    tile[i][j] = STREAM
+                                     ? __builtin_nontemporal_load(&src[row + i])
+                                     : src[row + i];
             }
         }
         __syncthreads();
@@ -325,7 +358,7 @@ __device__ __forceinline__ void tile_vs_body(
                     uint4 q;
                     ((T *)&q)[0] = tile[i][j2];
                     ((T *)&q)[1] = tile[i][j2 + 1];
-                    *(uint4 *)&row[j2] = q;
+                    vs_store16<STREAM>(&row[j2], q);
                 }
                 if ((nj & 1) && tx == 0) /* odd tail element */
                     row[nj - 1] = tile[i][nj - 1];
@@ -351,6 +384,21 @@ __global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs(
     if (bid >= nblocks) return;
     tile_vs_body<T, TI, TJ, NROWS, JCHUNK>(tile, src, dst, d, ta, ntile_i,
                                            njchunk, bid);
+}
+
+/* The streaming form (tile_vs_body's STREAM policy) under a name of its own,
+ * like k_copy_1d_nt: the plain kernel's symbols, and with them its rows in
+ * profiles and in the compiler's resource report, stay what they were. */
+template <typename T, int TI, int TJ, int NROWS, int JCHUNK>
+__global__ __launch_bounds__(64 * NROWS) void k_transpose_tile_vs_nt(
+    const T *__restrict__ src, T *__restrict__ dst, DescDev d, int ta,
+    int64_t ntile_i, int64_t njchunk, int64_t nblocks)
+{
+    __shared__ T tile[TI][TJ + 2];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    tile_vs_body<T, TI, TJ, NROWS, JCHUNK, true>(tile, src, dst, d, ta,
+                                                 ntile_i, njchunk, bid);
 }
 
 /* LDS-tiled transpose for 1- and 2-byte elements with PACKED (8-B) global
@@ -1300,6 +1348,7 @@ struct KernelSel {
     int word = 0;      /* bytes per kernel word */
     int byteified = 0; /* went through the byte-ify fallback */
     int sweep = 1;     /* j-tiles swept per workgroup (tile kernels) */
+    int stream = 0;    /* TILE_VS: nontemporal loads and vector stores */
     int ta = -1;       /* dst-contiguous axis (tile kernels) */
     int m = 1;         /* words per element (wide tile / word-expanded) */
     int ti = 0, tj = 0, pitch = 0; /* wide tile: shape (elements), LDS row
@@ -1317,6 +1366,20 @@ static int sweep_depth(int64_t nti, int64_t ntj, int64_t nbatch)
     if (ntj * nti * nbatch >= 8 * 4096 && ntj >= 64) return 8;
     return 1;
 }
+
+/* Payload bytes from which the vector-store tile streams
+ * (pa_set_stream_min_bytes; negative = never).  Probe rows behind the number
+ * (profiles/stream_tile_probe.txt, GB/s, control median and max against the
+ * streaming median, sweep depth by sweep_depth()):
+ *   128 MiB  6482 / 6526  vs 5840   loses (cache-resident)
+ *   256 MiB  5158 / 5193  vs 5883   wins
+ *   512 MiB  5018 / 5084  vs 5557   wins
+ *     1 GiB  5376 / 5441  vs 5803   wins
+ *     2 GiB  5640 / 5673  vs 5977   wins
+ *     8 GiB  5742 / 5821  vs 5941   wins
+ * The streaming median beats the control's max from 256 MiB up; below 512 MiB
+ * the gate takes 512 MiB, the k_copy_1d_nt gate. */
+static std::atomic<int64_t> g_stream_min_bytes{512ll << 20};
 
 static pa_status select_kernel(const CopyDescH &dn, int64_t esz,
                                const void *src, const void *dst,
@@ -1382,6 +1445,8 @@ static pa_status select_kernel(const CopyDescH &dn, int64_t esz,
                 out->kind = PA_KERNEL_TILE_VS;
                 out->sweep = sweep_depth((dn.dims[0] + 63) / 64,
                                          (dn.dims[ta] + 127) / 128, nbatch);
+                const int64_t smin = g_stream_min_bytes.load();
+                out->stream = smin >= 0 && dn.total * 8 >= smin;
                 return 0;
             }
         }
@@ -1739,9 +1804,18 @@ static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
         pa_status gst = grid2d(nblocks, 64 * NR, &grid);
         if (gst) return gst;
 #define LAUNCH_VS(JCV)                                                       \
-    hipLaunchKernelGGL((k_transpose_tile_vs<uint64_t, TI, TJ, NR, JCV>),     \
-                       grid, dim3(64, NR), 0, stream, (const uint64_t *)s,   \
-                       (uint64_t *)d, dd, ta, nti, njc, nblocks)
+    do {                                                                     \
+        if (k.stream)                                                        \
+            hipLaunchKernelGGL(                                              \
+                (k_transpose_tile_vs_nt<uint64_t, TI, TJ, NR, JCV>), grid,   \
+                dim3(64, NR), 0, stream, (const uint64_t *)s,                \
+                (uint64_t *)d, dd, ta, nti, njc, nblocks);                   \
+        else                                                                 \
+            hipLaunchKernelGGL(                                              \
+                (k_transpose_tile_vs<uint64_t, TI, TJ, NR, JCV>), grid,      \
+                dim3(64, NR), 0, stream, (const uint64_t *)s,                \
+                (uint64_t *)d, dd, ta, nti, njc, nblocks);                   \
+    } while (0)
         if (k.sweep == 32)
             LAUNCH_VS(32);
         else if (k.sweep == 8)
@@ -3688,6 +3762,28 @@ pa_status pa_copy_kernel_kind_comp(int nd, const int64_t *dims,
     out[3] = k.sweep;
     out[4] = k.m;
     return 0;
+}
+
+pa_status pa_copy_kernel_stream(int nd, const int64_t *dims,
+                                const int64_t *sstr, int64_t soff,
+                                const int64_t *dstr, int64_t doff,
+                                int64_t elem_size, const void *src,
+                                const void *dst, int64_t *out)
+{
+    if (!out) return fail("null output");
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (elem_size <= 0) return fail("bad elem_size");
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    KernelSel k;
+    pa_status st = select_kernel_comp(d, elem_size, 1, src, dst, &k);
+    if (st) return st;
+    *out = k.stream;
+    return 0;
+}
+
+int64_t pa_set_stream_min_bytes(int64_t min_bytes)
+{
+    return g_stream_min_bytes.exchange(min_bytes);
 }
 
 pa_status pa_device_copy_wire(int nd, const int64_t *dims,

@@ -45,6 +45,7 @@ def load() -> ctypes.CDLL:
     lib.pa_last_error.restype = ctypes.c_char_p
     lib.pa_pencil_length_local.restype = I64
     lib.pa_plan_stage_table_builds.restype = I64
+    lib.pa_set_stream_min_bytes.restype = I64
     _LIB = lib
     return lib
 
@@ -166,6 +167,30 @@ def copy_kernel_kind(desc, esz: int, src_ptr: int = 0,
         (I64 * nd)(*dstr), I64(doff), I64(esz), VP(src_ptr), VP(dst_ptr),
         out), "pa_copy_kernel_kind")
     return KernelKind(*(int(v) for v in out))
+
+
+def copy_kernel_stream(desc, esz: int, src_ptr: int = 0,
+                       dst_ptr: int = 0) -> int:
+    """1 when ``pa_device_copy`` runs ``desc`` on the streaming form of the
+    vector-store tile (nontemporal loads and vector stores), else 0
+    (pa_copy_kernel_stream; host-only, arguments of
+    :func:`copy_kernel_kind`)."""
+    lib = load()
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    out = I64()
+    _check(lib, lib.pa_copy_kernel_stream(
+        nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+        (I64 * nd)(*dstr), I64(doff), I64(esz), VP(src_ptr), VP(dst_ptr),
+        ctypes.byref(out)), "pa_copy_kernel_stream")
+    return int(out.value)
+
+
+def set_stream_min_bytes(min_bytes: int) -> int:
+    """Set the payload size from which the vector-store tile streams and
+    return the previous one (pa_set_stream_min_bytes): 0 = always where
+    eligible, negative = never.  Process-wide tuning and testing hook."""
+    return int(load().pa_set_stream_min_bytes(I64(min_bytes)))
 
 
 def device_copy(desc, esz: int, src_ptr: int, dst_ptr: int,
