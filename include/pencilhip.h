@@ -426,6 +426,51 @@ int pa_plan_stage_table_count(const pa_plan *p);
  * that leaves it unchanged was served from the cache. */
 int64_t pa_plan_stage_table_builds(const pa_plan *p);
 
+/* ---- split and join transposes ---------------------------------------- */
+/* A vector field lives in two forms: an array of structs A, n scalars of S
+ * bytes per element with the components fastest (the reference's
+ * PencilArray{SVector{n,S}}, here pa_plan_create_comp), and n separately
+ * allocated scalar arrays F_0 .. F_{n-1} (pa_transpose_execute_many).  A split
+ * transpose reads A on the input pencil and writes the F_c on the output
+ * pencil, a join transpose the reverse; with T the ordinary transposition and
+ * A[c] component c of A,
+ *     split:  F_c == T(A[c])      join:  A[c] == T(F_c)     bit for bit,
+ * whatever the process grid.  The reference has neither: a host interleaves
+ * or de-interleaves in a pass of its own.
+ *
+ * Both run on an ORDINARY SCALAR plan, pa_plan_create(.., S, ..) with S = 4, 8
+ * or 16, and n >= 2 is an argument of the call.  Staging buffers and messages
+ * are byte for byte those of the n-field plan applied to the component copies
+ * A[c]: pa_plan_buffer_sizes_many(p, n) and pa_plan_peer_message(p, n, k) hold
+ * unchanged, and staging MUST come from pa_plan_set_buffers.  So a split's
+ * unpack is pa_transpose_unpack_many, a join's pack is pa_transpose_pack_many,
+ * and either may face an ordinary n-field peer.  The layout change sits in
+ *   pack_split   every pack: A -> the n component slots of each send block;
+ *   local_split  the fused local copy A -> F_c;
+ *   local_join   the fused local copy F_c -> A;
+ *   unpack_join  every unpack: the n slots of each recv block -> A,
+ * one launch per block carrying all n components (pa_copy_kernel_kind_soa
+ * tells which kernel).  Ordering a foreign exchange is the host's job exactly
+ * as for the _many stages.  execute_split / execute_join run pack, the
+ * single-group exchange of pa_transpose_execute_many, local, unpack;
+ * pa_transpose_wait and pa_plan_stage_times work after them.
+ * Refused with an error: a PA_PLAN_ALIASED plan (the two sides have different
+ * element sizes and cannot alias), a keep plan, a wire plan, a plan with a
+ * scale set, a composite plan (ncomp > 1), n < 2, S not 4, 8 or 16. */
+pa_status pa_transpose_pack_split(pa_plan *p, int n, const void *src_aos,
+                                  void *stream);
+pa_status pa_transpose_local_split(pa_plan *p, int n, const void *src_aos,
+                                   void *const *dsts, void *stream);
+pa_status pa_transpose_local_join(pa_plan *p, int n, const void *const *srcs,
+                                  void *dst_aos, void *stream);
+pa_status pa_transpose_unpack_join(pa_plan *p, int n, void *dst_aos,
+                                   void *stream);
+pa_status pa_transpose_execute_split(pa_plan *p, int n, const void *src_aos,
+                                     void *const *dsts, void *stream);
+pa_status pa_transpose_execute_join(pa_plan *p, int n,
+                                    const void *const *srcs, void *dst_aos,
+                                    void *stream);
+
 /* ---- reductions (src/reductions.jl:9-38) ----------------------------- */
 /* One ncclAllReduce over a communicator (normally the FULL topology comm):
  * the collective behind the reference's mapreduce/any/all.
@@ -594,6 +639,52 @@ pa_status pa_copy_kernel_kind_scale(int nd, const int64_t *dims,
                                     int scalar, int64_t nscal,
                                     const void *src, const void *dst,
                                     int64_t out[5]);
+
+/* ---- split / join copies (split and join transposes) ------------------- */
+/* One strided-copy descriptor between an array of structs and n scalar
+ * fields (the kernels the split and join stages use).  The descriptor is the
+ * ordinary one of ONE component, in scalars of scalar_size bytes (4, 8 or
+ * 16).  The array of structs holds scalar c of element e at n*e + c.
+ * PA_SOA_SPLIT: the source side addresses `aos`, the destination side every
+ * fields[c], and fields[c][dst index] = aos[n * (src index) + c].
+ * PA_SOA_JOIN: the source side addresses every fields[c], the destination
+ * side `aos`, and aos[n * (dst index) + c] = fields[c][src index].
+ * All n + 1 pointers must be aligned to the scalar (16 bytes for a 16-byte
+ * one, which moves as one word), else the call fails; wider accesses are used
+ * only where the pointers, offsets and strides allow them. */
+#define PA_SOA_SPLIT 0
+#define PA_SOA_JOIN  1
+pa_status pa_device_copy_soa(int nd, const int64_t *dims, const int64_t *sstr,
+                             int64_t soff, const int64_t *dstr, int64_t doff,
+                             int64_t scalar_size, int n, int dir, void *aos,
+                             void *const *fields, void *stream);
+/* Which split / join kernel runs for this descriptor (host-only; the n + 1
+ * pointers are used for their alignment only, and fields may be NULL, taken
+ * as aligned).  out = {kind, V, tile_i, tile_j, sweep_depth}:
+ *  - n <= 4, n * scalar_size <= 64 and axis 0 contiguous on both sides (1-D
+ *    included): PA_KERNEL_SOA_LINEAR, a lane moving V consecutive elements: n
+ *    accesses of V scalars on the array-of-structs side and one per field.  V
+ *    starts at 16 / scalar_size and is halved down to 1 until it divides the
+ *    run dims[0], both offsets, every non-unit stride of both sides, and in
+ *    scalars the aos pointer and every field pointer;
+ *  - n <= 4, n * scalar_size <= 64, the source side contiguous along axis 0
+ *    and the destination side along an axis ta >= 1: PA_KERNEL_SOA_TILE, an
+ *    LDS transpose of tile_i (axis 0) x tile_j (ta) elements of n components,
+ *    the shape of PA_KERNEL_TILE_WIDE for elements of n * scalar_size bytes;
+ *  - otherwise PA_KERNEL_SOA_GENERIC, one lane per scalar: correct and slow;
+ *  - an empty descriptor: PA_KERNEL_NONE.
+ * V = 1 and tile = 0 where they do not apply; sweep_depth is 1.
+ * Errors: n < 2, scalar_size not 4, 8 or 16, an unknown dir, out == NULL, a
+ * pointer of a non-empty descriptor that is not aligned to the scalar. */
+#define PA_KERNEL_SOA_LINEAR  16
+#define PA_KERNEL_SOA_TILE    17
+#define PA_KERNEL_SOA_GENERIC 18
+pa_status pa_copy_kernel_kind_soa(int nd, const int64_t *dims,
+                                  const int64_t *sstr, int64_t soff,
+                                  const int64_t *dstr, int64_t doff,
+                                  int64_t scalar_size, int n, int dir,
+                                  const void *aos, const void *const *fields,
+                                  int64_t out[5]);
 
 /* ---- zero fill (truncated transposes) ---------------------------------- */
 /* Zero one destination-only window on the device (the kernel body a keep

@@ -24,12 +24,18 @@ from .array import PencilArray
 from .plan import (CopyDesc, FillDesc, TransposePlan, build_plan, fourier_keep,
                    normalize_desc)
 from .transpositions import (
+    JoinTransposition,
     MultiTransposition,
+    SplitTransposition,
     Transposition,
     run_transpose_sim,
+    run_transpose_sim_join,
     run_transpose_sim_many,
+    run_transpose_sim_split,
     transpose_into,
+    transpose_join_into,
     transpose_many_into,
+    transpose_split_into,
 )
 from .wire import round_wire
 from .scale import scale_array
@@ -46,6 +52,8 @@ __all__ = [
     "Topology", "dims_create", "Pencil", "PencilArray",
     "Transposition", "transpose_into", "run_transpose_sim", "ManyPencilArray",
     "MultiTransposition", "transpose_many_into", "run_transpose_sim_many",
+    "SplitTransposition", "JoinTransposition", "transpose_split_into",
+    "transpose_join_into", "run_transpose_sim_split", "run_transpose_sim_join",
     "MPIIOFile", "reductions", "round_wire", "scale_array",
     "gather", "gather_sim", "gather_dist",
     "CopyDesc", "TransposePlan", "build_plan", "normalize_desc",

@@ -56,6 +56,33 @@ def apply_copy_conv(desc: CopyDesc, src_scalars: np.ndarray,
     dv[...] = conv(sv)
 
 
+def apply_copy_soa(desc: CopyDesc, aos_scalars: np.ndarray,
+                   field: np.ndarray, n: int, c: int, split: bool) -> None:
+    """Component ``c`` of a split or join copy: ``desc`` is the descriptor of
+    one component in scalar units, and the array of structs holds scalar
+    ``c`` of element ``e`` at ``n*e + c``.  ``split``: the source side
+    addresses ``aos_scalars`` and the destination side ``field``; otherwise
+    the reverse."""
+    if desc.nelem == 0:
+        return
+    assert aos_scalars.ndim == 1 and field.ndim == 1
+    isz = field.itemsize
+    assert aos_scalars.itemsize == isz
+    astr, aoff = (desc.sstrides, desc.soffset) if split else \
+        (desc.dstrides, desc.doffset)
+    fstr, foff = (desc.dstrides, desc.doffset) if split else \
+        (desc.sstrides, desc.soffset)
+    av = np.lib.stride_tricks.as_strided(
+        aos_scalars[aoff * n + c:], shape=desc.dims,
+        strides=tuple(s * n * isz for s in astr))
+    fv = np.lib.stride_tricks.as_strided(
+        field[foff:], shape=desc.dims, strides=tuple(s * isz for s in fstr))
+    if split:
+        fv[...] = av
+    else:
+        av[...] = fv
+
+
 def apply_fill(desc: FillDesc, dst_flat: np.ndarray) -> None:
     """dst[doffset + Σ j·dstrides] = +0 (all zero bytes): the fill of a
     truncated transpose outside its keep set."""

@@ -1231,6 +1231,220 @@ __global__ __launch_bounds__(256) void k_scale_generic(
     }
 }
 
+/* ---- split / join kernels: vector-valued array <-> scalar fields ---------
+ *
+ * One side of the copy is an array of structs (AoS): n scalars of type S per
+ * element, components fastest, scalar c of element e at n*e + c.  The other
+ * side is n separately based scalar fields (SoA), field c holding component
+ * c.  SPLIT reads the AoS side and writes the fields, JOIN the reverse.  The
+ * descriptor is the ordinary one of ONE component in scalar-element units:
+ * its source side addresses the AoS array for a split and the fields for a
+ * join.  The field base pointers travel by value. */
+#define PA_SOA_TILE_MAX_N 4
+#define PA_SOA_TILE_TJ 16
+#define PA_SOA_GENERIC_PTRS 8
+template <int N> struct SoaPtrs { void *p[N]; };
+
+/* Axis 0 contiguous on both sides.  A lane owns V consecutive elements: the
+ * N*V AoS scalars are N aligned V-scalar vectors next to each other, and each
+ * field gets one V-scalar vector; the interleave between them happens in
+ * registers with compile-time indices.  The descriptor is in units of V
+ * scalars.  The N AoS accesses of a wave cover one contiguous range of
+ * 64*N*V scalars, every byte of it exactly once. */
+template <typename S, int DIR, int N, int V>
+__global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
+                                                    SoaPtrs<N> f, DescDev d)
+{
+    typedef VecT<S, V> SV;
+    const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t run = d.dims[0];
+    const int64_t idx = b * blockDim.x + threadIdx.x;
+    if (idx >= d.total) return;
+    int64_t o = idx / run;
+    const int64_t i = idx - o * run;
+    int64_t so = d.soff + i, doo = d.doff + i;
+    for (int ax = 1; ax < d.nd; ax++) {
+        const int64_t j = o % d.dims[ax];
+        o /= d.dims[ax];
+        so += j * d.sstr[ax];
+        doo += j * d.dstr[ax];
+    }
+    SV *aos = (SV *)aos_ + (DIR == PA_SOA_SPLIT ? so : doo) * N;
+    const int64_t fo = DIR == PA_SOA_SPLIT ? doo : so;
+    S flat[N * V]; /* scalar v*N + c: component c of the lane's element v */
+    if (DIR == PA_SOA_SPLIT) {
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            const SV in = aos[k];
+#pragma unroll
+            for (int j = 0; j < V; j++) flat[k * V + j] = in.v[j];
+        }
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            SV out;
+#pragma unroll
+            for (int v = 0; v < V; v++) out.v[v] = flat[v * N + c];
+            ((SV *)f.p[c])[fo] = out;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            const SV in = ((const SV *)f.p[c])[fo];
+#pragma unroll
+            for (int v = 0; v < V; v++) flat[v * N + c] = in.v[v];
+        }
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            SV out;
+#pragma unroll
+            for (int j = 0; j < V; j++) out.v[j] = flat[k * V + j];
+            aos[k] = out;
+        }
+    }
+}
+
+/* The permuted case: the source side is contiguous along axis 0, the
+ * destination side along axis ta.  One LDS tile of ti (axis 0) x tj (ta)
+ * elements x N components; tj is PA_SOA_TILE_TJ.  The AoS side moves rows of
+ * ni*N or nj*N contiguous scalars with the word-index sweep of
+ * k_transpose_tile_wide, q / N being a constant division.
+ *
+ * SPLIT: the tile is the wide tile's, word j*pitch + i*N + c, pitch >= ti*N.
+ * The AoS load writes consecutive LDS words.  The store puts lane
+ * (c, j) = (tx / tj, tx % tj) on field c along ta, so the N components share
+ * a wave (N*tj <= 64 lanes); with pitch == N (mod 256/W) its LDS words are
+ * i*N + j*N + c modulo the bank span: N*tj different consecutive words, which
+ * share a bank only where they wrap the span of 256/W words.
+ *
+ * JOIN: the tile is planar, word c*plane + j*pitch + i, pitch >= ti.  Each
+ * component tile is loaded like tile_body's (lanes along axis 0: consecutive
+ * LDS words).  The AoS store reads, at word index q = j*N + c of row i,
+ * c*plane + j*pitch + i; with plane == 1 and pitch == N (mod 256/W) that is
+ * q + i modulo the bank span: consecutive lanes, consecutive banks. */
+template <typename S, int DIR, int N>
+__global__ __launch_bounds__(256) void k_soa_tile(
+    void *__restrict__ aos_, SoaPtrs<N> f, DescDev d, int ta, int ti,
+    int pitch, int plane, int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+{
+    extern __shared__ uint4 soa_lds[];
+    S *tile = (S *)soa_lds;
+    constexpr int NR = 4;
+    constexpr int TJ = PA_SOA_TILE_TJ;
+    static_assert(N * TJ <= 64, "the components of a split store share a wave");
+
+    const int tx = threadIdx.x; /* 0..63 */
+    const int ty = threadIdx.y; /* 0..NR-1 */
+
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int64_t t_i = bid % ntile_i;
+    int64_t rest = bid / ntile_i;
+    const int64_t t_j = rest % ntile_j;
+    int64_t batch = rest / ntile_j;
+
+    int64_t so_b = d.soff, do_b = d.doff;
+    for (int a = 1; a < d.nd; a++) {
+        if (a == ta) continue;
+        const int64_t j = batch % d.dims[a];
+        batch /= d.dims[a];
+        so_b += j * d.sstr[a];
+        do_b += j * d.dstr[a];
+    }
+
+    const int64_t i0 = t_i * ti;
+    const int ni = (int)(d.dims[0] - i0 < ti ? d.dims[0] - i0 : ti);
+    const int64_t j0 = t_j * TJ;
+    const int nj = (int)(d.dims[ta] - j0 < TJ ? d.dims[ta] - j0 : TJ);
+    const int64_t sj = d.sstr[ta];
+    const int64_t di = d.dstr[0];
+
+    if (DIR == PA_SOA_SPLIT) {
+        /* load: lanes sweep the words of one AoS row, rows sweep ta */
+        {
+            const S *base = (const S *)aos_ + (so_b + i0 + j0 * sj) * N;
+            const int nw = ni * N;
+            for (int j = ty; j < nj; j += NR) {
+                const S *row = base + (int64_t)j * sj * N;
+                S *trow = tile + j * pitch;
+                for (int q = tx; q < nw; q += 64) trow[q] = row[q];
+            }
+        }
+        __syncthreads();
+        /* store: lane (c, j) writes field c along ta, rows sweep axis 0 */
+        {
+            const int c = tx / TJ, j = tx % TJ;
+            if (c < N && j < nj) {
+                S *dst = (S *)f.p[0];
+#pragma unroll
+                for (int cc = 1; cc < N; cc++)
+                    if (c == cc) dst = (S *)f.p[cc];
+                dst += do_b + j0 + i0 * di + j;
+                const S *tcol = tile + j * pitch + c;
+                for (int i = ty; i < ni; i += NR)
+                    dst[(int64_t)i * di] = tcol[i * N];
+            }
+        }
+    } else {
+        /* load: per component, lanes sweep axis 0, rows sweep ta */
+        {
+            const int64_t fbase = so_b + i0 + j0 * sj;
+#pragma unroll
+            for (int c = 0; c < N; c++) {
+                const S *src = (const S *)f.p[c] + fbase;
+                for (int j = ty; j < nj; j += NR) {
+                    const S *row = src + (int64_t)j * sj;
+                    S *trow = tile + c * plane + j * pitch;
+                    for (int i = tx; i < ni; i += 64) trow[i] = row[i];
+                }
+            }
+        }
+        __syncthreads();
+        /* store: lanes sweep the words of one AoS row, rows sweep axis 0 */
+        {
+            S *base = (S *)aos_ + (do_b + j0 + i0 * di) * N;
+            const int nw = nj * N;
+            for (int i = ty; i < ni; i += NR) {
+                S *row = base + (int64_t)i * di * N;
+                for (int q = tx; q < nw; q += 64) {
+                    const int j = q / N, c = q - j * N;
+                    row[q] = tile[c * plane + j * pitch + i];
+                }
+            }
+        }
+    }
+}
+
+/* Any other descriptor, any n: one lane per scalar, grid-stride like
+ * k_copy_generic.  blockIdx.z is the component within this launch's chunk of
+ * at most PA_SOA_GENERIC_PTRS fields, whose first component is c0. */
+template <typename S, int DIR>
+__global__ __launch_bounds__(256) void k_soa_generic(
+    void *__restrict__ aos_, SoaPtrs<PA_SOA_GENERIC_PTRS> f, DescDev d, int n,
+    int c0)
+{
+    const int c = blockIdx.z;
+    S *fp = (S *)f.p[0];
+#pragma unroll
+    for (int cc = 1; cc < PA_SOA_GENERIC_PTRS; cc++)
+        if (c == cc) fp = (S *)f.p[cc];
+    S *aos = (S *)aos_ + c0 + c;
+    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; idx < d.total; idx += stride) {
+        int64_t rem = idx, so = d.soff, doo = d.doff;
+        for (int a = 0; a < d.nd; a++) {
+            const int64_t j = rem % d.dims[a];
+            rem /= d.dims[a];
+            so += j * d.sstr[a];
+            doo += j * d.dstr[a];
+        }
+        if (DIR == PA_SOA_SPLIT)
+            fp[doo] = aos[so * n];
+        else
+            aos[doo * n] = fp[so];
+    }
+}
+
 /* ================= descriptor normalization & dispatch ============= */
 
 struct CopyDescH {
@@ -2295,6 +2509,223 @@ static pa_status launch_scale_sel(const CvtSel &k, const void *src, void *dst,
     if (k.scalar == PA_SCALAR_F64)
         return launch_scale_sel_t<double>(k, src, dst, alpha, stream);
     return fail("bad scalar type %d", k.scalar);
+}
+
+/* ---- split / join copies: selection and launch ------------------------ */
+
+/* The decision for a split or join copy, made in ONE place like
+ * select_kernel(): launch_soa_sel() executes it, pa_copy_kernel_kind_soa()
+ * reports it. */
+struct SoaSel {
+    int kind = PA_KERNEL_NONE;
+    int ssz = 0, n = 0, dir = 0;
+    int V = 1;          /* scalars per access (linear) */
+    int ti = 0, tj = 0; /* tile shape in elements (tile) */
+    int pitch = 0, plane = 0; /* LDS row pitch and component plane, words */
+    int ta = -1;        /* dst-contiguous axis (tile) */
+    CopyDescH d;        /* linear: in units of V scalars; else scalars */
+};
+
+static pa_status check_soa(int64_t scalar_size, int n, int dir)
+{
+    if (n < 2) return fail("n must be >= 2 (got %d)", n);
+    if (scalar_size != 4 && scalar_size != 8 && scalar_size != 16)
+        return fail("invalid scalar_size %lld for a split or join: must be "
+                    "4, 8 or 16", (long long)scalar_size);
+    if (dir != PA_SOA_SPLIT && dir != PA_SOA_JOIN)
+        return fail("unknown direction %d: PA_SOA_SPLIT or PA_SOA_JOIN", dir);
+    return 0;
+}
+
+static pa_status select_kernel_soa(const CopyDescH &dn, int64_t ssz, int n,
+                                   int dir, const void *aos,
+                                   const void *const *fields, SoaSel *out)
+{
+    if (pa_status st = check_soa(ssz, n, dir)) return st;
+    *out = SoaSel();
+    out->ssz = (int)ssz;
+    out->n = n;
+    out->dir = dir;
+    if (dn.total == 0) return 0;
+    out->d = dn;
+    /* every kernel accesses whole scalars (a 16-byte one as uint4) */
+    if ((uintptr_t)aos % (uintptr_t)ssz)
+        return fail("the vector-valued array pointer is not aligned to the "
+                    "%lld-byte scalar", (long long)ssz);
+    for (int c = 0; fields && c < n; c++)
+        if ((uintptr_t)fields[c] % (uintptr_t)ssz)
+            return fail("the pointer of field %d is not aligned to the "
+                        "%lld-byte scalar", c, (long long)ssz);
+    const bool small = n <= PA_SOA_TILE_MAX_N &&
+                       (int64_t)n * ssz <= PA_WIDE_MAX_BYTES;
+
+    if (small && dn.sstr[0] == 1 && dn.dstr[0] == 1) {
+        /* V scalars per access, each access naturally aligned on both
+         * sides: V divides the run, both offsets, every non-unit stride and
+         * (in scalars) the AoS base and every field base.  The AoS offset
+         * n * (element offset) follows the element offset. */
+        uintptr_t ptrs = (uintptr_t)aos;
+        for (int c = 0; c < n; c++) ptrs |= (uintptr_t)(fields ? fields[c] : 0);
+        CopyDescH w = dn;
+        int64_t V = 16 / ssz;
+        auto ok = [&](int64_t v) {
+            if (w.dims[0] % v || w.soff % v || w.doff % v) return false;
+            if (ptrs % (uintptr_t)(v * ssz)) return false;
+            for (int a = 1; a < w.nd; a++)
+                if (w.sstr[a] % v || w.dstr[a] % v) return false;
+            return true;
+        };
+        while (V > 1 && !ok(V)) V >>= 1;
+        w.dims[0] /= V;
+        w.soff /= V;
+        w.doff /= V;
+        for (int a = 1; a < w.nd; a++) {
+            w.sstr[a] /= V;
+            w.dstr[a] /= V;
+        }
+        w.total = 1;
+        for (int a = 0; a < w.nd; a++) w.total *= w.dims[a];
+        out->kind = PA_KERNEL_SOA_LINEAR;
+        out->V = (int)V;
+        out->d = w;
+        return 0;
+    }
+
+    int ta = -1;
+    if (dn.sstr[0] == 1)
+        for (int a = 1; a < dn.nd; a++)
+            if (dn.dstr[a] == 1) { ta = a; break; }
+    if (small && ta > 0) {
+        out->kind = PA_KERNEL_SOA_TILE;
+        out->ta = ta;
+        wide_tile_shape(n * ssz, &out->ti, &out->tj);
+        /* LDS pitch == n modulo the 256-B bank span (in words), and for a
+         * join's planar tile plane == 1: see k_soa_tile */
+        const int64_t span = 256 / ssz;
+        const int64_t row = dir == PA_SOA_SPLIT ? (int64_t)out->ti * n : out->ti;
+        out->pitch = (int)(n + (row - n + span - 1) / span * span);
+        if (dir == PA_SOA_JOIN)
+            out->plane = (int)(1 + ((int64_t)out->tj * out->pitch - 1 +
+                                    span - 1) / span * span);
+        return 0;
+    }
+    out->kind = PA_KERNEL_SOA_GENERIC;
+    return 0;
+}
+
+template <typename S, int DIR, int N>
+static pa_status launch_soa_n(const SoaSel &k, void *aos, void *const *fields,
+                              hipStream_t stream)
+{
+    SoaPtrs<N> f;
+    for (int c = 0; c < N; c++) f.p[c] = fields[c];
+    DescDev dd = to_dev(k.d);
+    dim3 grid;
+    if (k.kind == PA_KERNEL_SOA_LINEAR) {
+        if (pa_status gst = grid2d(grid_exact(k.d.total, 256), 256, &grid))
+            return gst;
+        constexpr int VMAX = 16 / (int)sizeof(S);
+#define SOA_LIN(VV)                                                          \
+    hipLaunchKernelGGL((k_soa_linear<S, DIR, N, VV>), grid, dim3(256), 0,    \
+                       stream, aos, f, dd)
+        if (k.V < 1 || k.V > VMAX) return fail("bad vector width %d", k.V);
+        if constexpr (VMAX >= 4) {
+            if (k.V == 4) { SOA_LIN(4); return 0; }
+        }
+        if constexpr (VMAX >= 2) {
+            if (k.V == 2) { SOA_LIN(2); return 0; }
+        }
+        if (k.V != 1) return fail("bad vector width %d", k.V);
+        SOA_LIN(1);
+#undef SOA_LIN
+        return 0;
+    }
+    /* PA_KERNEL_SOA_TILE */
+    const CopyDescH &dn = k.d;
+    const int64_t row = DIR == PA_SOA_SPLIT ? (int64_t)k.ti * N : k.ti;
+    if (k.ta < 1 || k.ti < 1 || k.tj != PA_SOA_TILE_TJ || k.pitch < row ||
+        (DIR == PA_SOA_JOIN && k.plane < k.tj * k.pitch))
+        return fail("bad split/join tile selection");
+    int64_t nbatch = 1;
+    for (int a = 1; a < dn.nd; a++)
+        if (a != k.ta) nbatch *= dn.dims[a];
+    const int64_t nti = (dn.dims[0] + k.ti - 1) / k.ti;
+    const int64_t ntj = (dn.dims[k.ta] + k.tj - 1) / k.tj;
+    const int64_t nblocks = nti * ntj * nbatch;
+    if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
+    const size_t lds = sizeof(S) * (DIR == PA_SOA_SPLIT
+                                        ? (size_t)k.tj * k.pitch
+                                        : (size_t)N * k.plane);
+    if (lds > (64u << 10))
+        return fail("split/join tile needs %zu B of LDS", lds);
+    hipLaunchKernelGGL((k_soa_tile<S, DIR, N>), grid, dim3(64, 4), lds,
+                       stream, aos, f, dd, k.ta, k.ti, k.pitch, k.plane, nti,
+                       ntj, nblocks);
+    return 0;
+}
+
+template <typename S, int DIR>
+static pa_status launch_soa_t(const SoaSel &k, void *aos, void *const *fields,
+                              hipStream_t stream)
+{
+    if (k.kind == PA_KERNEL_SOA_GENERIC) {
+        /* grid-stride kernel, at most PA_SOA_GENERIC_PTRS fields a launch */
+        DescDev dd = to_dev(k.d);
+        const int gx = grid_for(k.d.total, 256);
+        for (int c0 = 0; c0 < k.n; c0 += PA_SOA_GENERIC_PTRS) {
+            const int nc = std::min(k.n - c0, PA_SOA_GENERIC_PTRS);
+            SoaPtrs<PA_SOA_GENERIC_PTRS> f;
+            for (int c = 0; c < PA_SOA_GENERIC_PTRS; c++)
+                f.p[c] = c < nc ? fields[c0 + c] : nullptr;
+            hipLaunchKernelGGL((k_soa_generic<S, DIR>), dim3(gx, 1, nc),
+                               dim3(256), 0, stream, aos, f, dd, k.n, c0);
+        }
+        return 0;
+    }
+    switch (k.n) {
+    case 2: return launch_soa_n<S, DIR, 2>(k, aos, fields, stream);
+    case 3: return launch_soa_n<S, DIR, 3>(k, aos, fields, stream);
+    case 4: return launch_soa_n<S, DIR, 4>(k, aos, fields, stream);
+    default: return fail("bad split/join selection: n = %d", k.n);
+    }
+}
+
+/* aos is the source of a split and the destination of a join */
+static pa_status launch_soa_sel(const SoaSel &k, void *aos,
+                                void *const *fields, hipStream_t stream)
+{
+    if (k.kind == PA_KERNEL_NONE) return 0;
+    if (k.kind != PA_KERNEL_SOA_LINEAR && k.kind != PA_KERNEL_SOA_TILE &&
+        k.kind != PA_KERNEL_SOA_GENERIC)
+        return fail("bad split/join kernel kind %d", k.kind);
+    pa_status st;
+#define SOA_DIR(S)                                                           \
+    (k.dir == PA_SOA_SPLIT ? launch_soa_t<S, PA_SOA_SPLIT>(k, aos, fields,   \
+                                                           stream)          \
+                           : launch_soa_t<S, PA_SOA_JOIN>(k, aos, fields,    \
+                                                          stream))
+    if (k.ssz == 4)
+        st = SOA_DIR(uint32_t);
+    else if (k.ssz == 8)
+        st = SOA_DIR(uint64_t);
+    else if (k.ssz == 16)
+        st = SOA_DIR(uint4);
+    else
+        return fail("bad scalar size %d", k.ssz);
+#undef SOA_DIR
+    if (st) return st;
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static pa_status launch_desc_soa(const CopyDescH &dn, int64_t ssz, int n,
+                                 int dir, void *aos, void *const *fields,
+                                 hipStream_t stream)
+{
+    SoaSel k;
+    if (pa_status st = select_kernel_soa(dn, ssz, n, dir, aos, fields, &k))
+        return st;
+    return launch_soa_sel(k, aos, fields, stream);
 }
 
 /* ---- zero fill: descriptor, store width, launch ----------------------- */
@@ -4386,6 +4817,35 @@ static pa_status many_check(const pa_plan *p, int n, int stage,
     return 0;
 }
 
+/* The single-group exchange of n fields: one message per peer at the
+ * pa_plan_peer_message ranges, on the comm stream, ordered after the packs
+ * already enqueued on `stream`; ev_comm is recorded behind it. */
+static pa_status exchange_many(pa_plan *p, int n, hipStream_t stream)
+{
+    if (pa_status st = ensure_comm_stream(p)) return st;
+    HIP_CHECK(hipEventRecord(p->ev_pack, stream));
+    HIP_CHECK(hipStreamWaitEvent(p->comm_stream, p->ev_pack, 0));
+    TM_REC(3, p->comm_stream);
+    NCCL_CHECK(ncclGroupStart());
+    for (auto &blk : p->peers) {
+        if (blk.k == p->myk) continue;
+        int64_t m[4];
+        if (pa_status st = pa_plan_peer_message(p, n, blk.k, m)) return st;
+        if (m[3])
+            NCCL_CHECK(ncclRecv((char *)p->recv_buf + m[2], (size_t)m[3],
+                                ncclUint8, blk.k, p->comm->comm,
+                                p->comm_stream));
+        if (m[1])
+            NCCL_CHECK(ncclSend((const char *)p->send_buf + m[0],
+                                (size_t)m[1], ncclUint8, blk.k,
+                                p->comm->comm, p->comm_stream));
+    }
+    NCCL_CHECK(ncclGroupEnd());
+    TM_REC(4, p->comm_stream);
+    HIP_CHECK(hipEventRecord(p->ev_comm, p->comm_stream));
+    return 0;
+}
+
 static pa_status run_stage(pa_plan *p, int n, int stage,
                            const void *const *srcs, void *const *dsts,
                            hipStream_t stream)
@@ -4641,30 +5101,8 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
 
     /* 2. one grouped exchange, one message per peer carrying all n fields,
      * on the comm stream, event-ordered like pa_transpose_execute */
-    if (xchg) {
-        if (pa_status st = ensure_comm_stream(p)) return st;
-        HIP_CHECK(hipEventRecord(p->ev_pack, stream));
-        HIP_CHECK(hipStreamWaitEvent(p->comm_stream, p->ev_pack, 0));
-        TM_REC(3, p->comm_stream);
-        NCCL_CHECK(ncclGroupStart());
-        for (auto &blk : p->peers) {
-            if (blk.k == p->myk) continue;
-            int64_t m[4];
-            if (pa_status st = pa_plan_peer_message(p, n, blk.k, m))
-                return st;
-            if (m[3])
-                NCCL_CHECK(ncclRecv((char *)p->recv_buf + m[2], (size_t)m[3],
-                                    ncclUint8, blk.k, p->comm->comm,
-                                    p->comm_stream));
-            if (m[1])
-                NCCL_CHECK(ncclSend((const char *)p->send_buf + m[0],
-                                    (size_t)m[1], ncclUint8, blk.k,
-                                    p->comm->comm, p->comm_stream));
-        }
-        NCCL_CHECK(ncclGroupEnd());
-        TM_REC(4, p->comm_stream);
-        HIP_CHECK(hipEventRecord(p->ev_comm, p->comm_stream));
-    }
+    if (xchg)
+        if (pa_status st = exchange_many(p, n, stream)) return st;
 
     /* 3. fused local copies (aliased: staged self unpacks), overlapping the
      * exchange on the caller's stream */
@@ -4678,8 +5116,221 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
     if (pa_status st = run_stage(p, n, STAGE_UNPACK, nullptr, dsts, stream))
         return st;
     TM_REC(6, stream);
+    return 0;
+}
+
+} /* extern "C" */
+
+/* ---- split and join transposes ----------------------------------------
+ *
+ * An ordinary scalar plan run with a vector-valued array on one side: n
+ * scalars per element, components fastest.  The staging layout is the
+ * multi-field one with the components as fields, so the opposite side's
+ * stages are pa_transpose_*_many unchanged.  One launch per block, each
+ * carrying all n components. */
+
+static pa_status soa_check(const pa_plan *p, int n, const void *aos,
+                           const void *const *fields, bool need_fields)
+{
+    if (!p) return fail("null plan");
+    if (n < 2) return fail("n must be >= 2 (got %d)", n);
+    if (p->aliased)
+        return fail("a split or join cannot run on a PA_PLAN_ALIASED plan: "
+                    "the two sides have different element sizes and cannot "
+                    "alias");
+    if (p->keep) return fail("a split or join cannot run on a keep plan");
+    if (p->wire) return fail("a split or join cannot run on a wire plan");
+    if (p->scale)
+        return fail("a split or join cannot run on a plan with a scale set");
+    if (p->ncomp > 1)
+        return fail("a split or join needs a scalar plan: this one has "
+                    "ncomp = %lld", (long long)p->ncomp);
+    if (pa_status st = check_soa(p->ssz, n, PA_SOA_SPLIT)) return st;
+    if (!aos) return fail("null vector-valued array pointer");
+    if (need_fields) {
+        if (!fields) return fail("null field pointers");
+        for (int c = 0; c < n; c++)
+            if (!fields[c]) return fail("null pointer for field %d", c);
+    }
+    if (p->own_bufs)
+        return fail("split and join stages need staging buffers of "
+                    "pa_plan_buffer_sizes_many bytes from pa_plan_set_buffers");
+    if ((p->send_total > 0 && !p->send_buf) ||
+        (p->recv_total > 0 && !p->recv_buf))
+        return fail("missing staging buffers: call pa_plan_set_buffers with "
+                    "pa_plan_buffer_sizes_many bytes");
+    return 0;
+}
+
+/* one staged block with the vector-valued array on its other side: component
+ * c's slot starts c * (block count) scalars into the block */
+static pa_status soa_staged(const pa_plan *p, int n, int dir, const SubC &sb,
+                            void *aos, void *staging, hipStream_t stream)
+{
+    CopyDescH d = sb.d;
+    const int64_t sh = many_shift(n, 0, sb.off, sb.n);
+    if (dir == PA_SOA_SPLIT)
+        d.doff += sh;
+    else
+        d.soff += sh;
+    void *few[PA_SOA_GENERIC_PTRS];
+    std::vector<void *> many;
+    void **slots = few;
+    if (n > PA_SOA_GENERIC_PTRS) {
+        many.resize(n);
+        slots = many.data();
+    }
+    for (int c = 0; c < n; c++)
+        slots[c] = (char *)staging + (int64_t)c * sb.n * p->ssz;
+    return launch_desc_soa(d, p->ssz, n, dir, aos, slots, stream);
+}
+
+extern "C" {
+
+pa_status pa_device_copy_soa(int nd, const int64_t *dims, const int64_t *sstr,
+                             int64_t soff, const int64_t *dstr, int64_t doff,
+                             int64_t scalar_size, int n, int dir, void *aos,
+                             void *const *fields, void *stream)
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_soa(scalar_size, n, dir)) return st;
+    if (!aos || !fields) return fail("null pointer");
+    for (int c = 0; c < n; c++)
+        if (!fields[c]) return fail("null pointer for field %d", c);
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    return launch_desc_soa(d, scalar_size, n, dir, aos, fields,
+                           (hipStream_t)stream);
+}
+
+pa_status pa_copy_kernel_kind_soa(int nd, const int64_t *dims,
+                                  const int64_t *sstr, int64_t soff,
+                                  const int64_t *dstr, int64_t doff,
+                                  int64_t scalar_size, int n, int dir,
+                                  const void *aos, const void *const *fields,
+                                  int64_t out[5])
+{
+    if (!out) return fail("null output");
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_soa(scalar_size, n, dir)) return st;
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    SoaSel k;
+    if (pa_status st =
+            select_kernel_soa(d, scalar_size, n, dir, aos, fields, &k))
+        return st;
+    out[0] = k.kind;
+    out[1] = k.V;
+    out[2] = k.ti;
+    out[3] = k.tj;
+    out[4] = 1; /* the split/join tile sweeps one tile per workgroup */
+    return 0;
+}
+
+pa_status pa_transpose_pack_split(pa_plan *p, int n, const void *src_aos,
+                                  void *stream)
+{
+    if (pa_status st = soa_check(p, n, src_aos, nullptr, false)) return st;
+    for (auto &b : p->peers)
+        for (auto &sb : b.pack)
+            if (pa_status st =
+                    soa_staged(p, n, PA_SOA_SPLIT, sb, (void *)src_aos,
+                               p->send_buf, (hipStream_t)stream))
+                return st;
+    return 0;
+}
+
+pa_status pa_transpose_local_split(pa_plan *p, int n, const void *src_aos,
+                                   void *const *dsts, void *stream)
+{
+    if (pa_status st = soa_check(p, n, src_aos, dsts, true)) return st;
+    for (auto &sb : p->local)
+        if (pa_status st =
+                launch_desc_soa(sb.d, p->ssz, n, PA_SOA_SPLIT,
+                                (void *)src_aos, dsts, (hipStream_t)stream))
+            return st;
+    return 0;
+}
+
+pa_status pa_transpose_local_join(pa_plan *p, int n, const void *const *srcs,
+                                  void *dst_aos, void *stream)
+{
+    if (pa_status st = soa_check(p, n, dst_aos, srcs, true)) return st;
+    for (auto &sb : p->local)
+        if (pa_status st =
+                launch_desc_soa(sb.d, p->ssz, n, PA_SOA_JOIN, dst_aos,
+                                (void *const *)srcs, (hipStream_t)stream))
+            return st;
+    return 0;
+}
+
+pa_status pa_transpose_unpack_join(pa_plan *p, int n, void *dst_aos,
+                                   void *stream)
+{
+    if (pa_status st = soa_check(p, n, dst_aos, nullptr, false)) return st;
+    for (auto &b : p->peers)
+        for (auto &sb : b.unpack)
+            if (pa_status st = soa_staged(p, n, PA_SOA_JOIN, sb, dst_aos,
+                                          p->recv_buf, (hipStream_t)stream))
+                return st;
+    return 0;
+}
+
+/* the hop shared by both: pack, the single-group exchange of
+ * pa_transpose_execute_many, local, unpack; exactly one of src_aos / dst_aos
+ * is set */
+static pa_status execute_soa(pa_plan *p, int n, const void *src_aos,
+                             const void *const *srcs, void *dst_aos,
+                             void *const *dsts, hipStream_t stream)
+{
+    const bool split = src_aos != nullptr;
+    if (pa_status st = soa_check(p, n, split ? src_aos : dst_aos,
+                                 split ? (const void *const *)dsts : srcs,
+                                 true))
+        return st;
+    const bool xchg = exchanging(p);
+    if (xchg && !p->comm)
+        return fail("subgroup exchange requires pa_plan_set_comm");
+    if (pa_status st = timing_begin(p)) return st;
+
+    TM_REC(0, stream);
+    if (pa_status st = split ? pa_transpose_pack_split(p, n, src_aos, stream)
+                             : pa_transpose_pack_many(p, n, srcs, stream))
+        return st;
+    TM_REC(1, stream);
+
+    if (xchg)
+        if (pa_status st = exchange_many(p, n, stream)) return st;
+
+    if (pa_status st =
+            split ? pa_transpose_local_split(p, n, src_aos, dsts, stream)
+                  : pa_transpose_local_join(p, n, srcs, dst_aos, stream))
+        return st;
+    TM_REC(2, stream);
+
+    if (xchg) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
+    TM_REC(5, stream);
+    if (pa_status st = split ? pa_transpose_unpack_many(p, n, dsts, stream)
+                             : pa_transpose_unpack_join(p, n, dst_aos, stream))
+        return st;
+    TM_REC(6, stream);
 #undef TM_REC
     return 0;
+}
+
+pa_status pa_transpose_execute_split(pa_plan *p, int n, const void *src_aos,
+                                     void *const *dsts, void *stream)
+{
+    if (!src_aos) return fail("null vector-valued array pointer");
+    return execute_soa(p, n, src_aos, nullptr, nullptr, dsts,
+                       (hipStream_t)stream);
+}
+
+pa_status pa_transpose_execute_join(pa_plan *p, int n,
+                                    const void *const *srcs, void *dst_aos,
+                                    void *stream)
+{
+    if (!dst_aos) return fail("null vector-valued array pointer");
+    return execute_soa(p, n, nullptr, srcs, dst_aos, nullptr,
+                       (hipStream_t)stream);
 }
 
 } /* extern "C" */

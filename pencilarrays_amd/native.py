@@ -76,6 +76,11 @@ FILL_NONE, FILL_ZERO = 0, 1
 KERNEL_SCALE_LINEAR = 13
 KERNEL_SCALE_TILE = 14
 KERNEL_SCALE_GENERIC = 15
+# split / join kernels (pa_copy_kernel_kind_soa) and their directions
+KERNEL_SOA_LINEAR = 16
+KERNEL_SOA_TILE = 17
+KERNEL_SOA_GENERIC = 18
+SOA_SPLIT, SOA_JOIN = 0, 1
 # real scalar types of a scale (pa_plan_set_scale)
 SCALAR_F32, SCALAR_F64 = 1, 2
 SCALAR_BYTES = {SCALAR_F32: 4, SCALAR_F64: 8}
@@ -88,6 +93,8 @@ KERNEL_NAMES = {
     KERNEL_CVT_TILE: "CVT_TILE", KERNEL_CVT_GENERIC: "CVT_GENERIC",
     KERNEL_FILL: "FILL", KERNEL_SCALE_LINEAR: "SCALE_LINEAR",
     KERNEL_SCALE_TILE: "SCALE_TILE", KERNEL_SCALE_GENERIC: "SCALE_GENERIC",
+    KERNEL_SOA_LINEAR: "SOA_LINEAR", KERNEL_SOA_TILE: "SOA_TILE",
+    KERNEL_SOA_GENERIC: "SOA_GENERIC",
 }
 
 # wire pairs (stored -> wire) and ops of a converting copy
@@ -270,6 +277,48 @@ def device_copy_scale(desc, scalar: int, nscal: int, alpha: float,
         (I64 * nd)(*dstr), I64(doff), int(scalar), I64(nscal),
         ctypes.c_double(alpha), VP(src_ptr), VP(dst_ptr), VP(stream)),
         "pa_device_copy_scale")
+
+
+def _soa_args(desc, scalar_size: int, n: int, direction: int, aos_ptr: int,
+              field_ptrs):
+    dims, sstr, soff, dstr, doff = _desc_fields(desc)
+    nd = len(dims)
+    if field_ptrs is None:
+        fields = None
+    else:
+        if len(field_ptrs) != n:
+            raise ValueError(f"expected {n} field pointers, got "
+                             f"{len(field_ptrs)}")
+        fields = (VP * n)(*[VP(int(q)) for q in field_ptrs])
+    return (nd, (I64 * nd)(*dims), (I64 * nd)(*sstr), I64(soff),
+            (I64 * nd)(*dstr), I64(doff), I64(scalar_size), int(n),
+            int(direction), VP(aos_ptr), fields)
+
+
+def copy_kernel_kind_soa(desc, scalar_size: int, n: int, direction: int,
+                         aos_ptr: int = 0,
+                         field_ptrs=None) -> WireKernelKind:
+    """Which split / join kernel ``pa_device_copy_soa`` / a split or join
+    stage launches for ``desc`` (the descriptor of one component, in scalars
+    of ``scalar_size`` bytes) between an array of ``n``-scalar structs and
+    ``n`` fields; ``direction`` is SOA_SPLIT or SOA_JOIN.  Host-only; the
+    pointers (``field_ptrs`` optional) are used for their alignment only.
+    The fields are those of :func:`copy_kernel_kind_wire`."""
+    lib = load()
+    out = (I64 * 5)()
+    _check(lib, lib.pa_copy_kernel_kind_soa(
+        *_soa_args(desc, scalar_size, n, direction, aos_ptr, field_ptrs),
+        out), "pa_copy_kernel_kind_soa")
+    return WireKernelKind(*(int(v) for v in out))
+
+
+def device_copy_soa(desc, scalar_size: int, n: int, direction: int,
+                    aos_ptr: int, field_ptrs, stream: int = 0) -> None:
+    """Run one split or join copy on the device (pa_device_copy_soa)."""
+    lib = load()
+    _check(lib, lib.pa_device_copy_soa(
+        *_soa_args(desc, scalar_size, n, direction, aos_ptr, field_ptrs),
+        VP(stream)), "pa_device_copy_soa")
 
 
 class FillKernelKind(NamedTuple):
@@ -585,6 +634,42 @@ class NativePlan:
             self._plan, n, self._ptrs(src_ptrs, n), self._ptrs(dst_ptrs, n),
             VP(stream)), "pa_transpose_execute_many")
 
+    # split and join transposes: ``n`` components on an ordinary scalar plan
+
+    def pack_split(self, n: int, src_aos_ptr: int, stream: int = 0):
+        _check(self.lib, self.lib.pa_transpose_pack_split(
+            self._plan, n, VP(src_aos_ptr), VP(stream)),
+            "pa_transpose_pack_split")
+
+    def local_split(self, src_aos_ptr: int, dst_ptrs, stream: int = 0):
+        n = len(dst_ptrs)
+        _check(self.lib, self.lib.pa_transpose_local_split(
+            self._plan, n, VP(src_aos_ptr), self._ptrs(dst_ptrs, n),
+            VP(stream)), "pa_transpose_local_split")
+
+    def local_join(self, src_ptrs, dst_aos_ptr: int, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_local_join(
+            self._plan, n, self._ptrs(src_ptrs, n), VP(dst_aos_ptr),
+            VP(stream)), "pa_transpose_local_join")
+
+    def unpack_join(self, n: int, dst_aos_ptr: int, stream: int = 0):
+        _check(self.lib, self.lib.pa_transpose_unpack_join(
+            self._plan, n, VP(dst_aos_ptr), VP(stream)),
+            "pa_transpose_unpack_join")
+
+    def execute_split(self, src_aos_ptr: int, dst_ptrs, stream: int = 0):
+        n = len(dst_ptrs)
+        _check(self.lib, self.lib.pa_transpose_execute_split(
+            self._plan, n, VP(src_aos_ptr), self._ptrs(dst_ptrs, n),
+            VP(stream)), "pa_transpose_execute_split")
+
+    def execute_join(self, src_ptrs, dst_aos_ptr: int, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_execute_join(
+            self._plan, n, self._ptrs(src_ptrs, n), VP(dst_aos_ptr),
+            VP(stream)), "pa_transpose_execute_join")
+
     def stage_table_count(self) -> int:
         """Stage tables in the plan's cache (pa_plan_stage_table_count)."""
         return int(self.lib.pa_plan_stage_table_count(self._plan))
@@ -896,16 +981,20 @@ class NativeMultiTransposition:
     re-pointed when the pool grows, like NativeTransposition."""
 
     def __init__(self, mt):
+        src = mt.srcs[0]
+        self._setup(_native_plan_for(mt.plan, src, getattr(mt, "wire", None),
+                                     getattr(mt, "wire_grouped", False),
+                                     getattr(mt, "scale", None)),
+                    mt.plan, len(mt.srcs), src.data.device)
+
+    def _setup(self, native_plan: NativePlan, plan, n: int, dev):
+        """Staging for ``n`` fields of ``native_plan`` on device ``dev`` and
+        the subgroup communicator of ``plan`` (the Python plan it mirrors)."""
         import torch
         self.torch = torch
-        plan = mt.plan
-        src = mt.srcs[0]
-        self.n = len(mt.srcs)
-        self.native = _native_plan_for(plan, src, getattr(mt, "wire", None),
-                                       getattr(mt, "wire_grouped", False),
-                                       getattr(mt, "scale", None))
+        self.n = n
+        self.native = native_plan
         sb, rb = self.native.buffer_sizes_many(self.n)
-        dev = src.data.device
         self._need = (max(sb, 1), max(rb, 1))
         if os.environ.get("PENCILHIP_PRIVATE_STAGING") == "1":
             self._pool = None
@@ -944,5 +1033,35 @@ class NativeMultiTransposition:
         stream = torch.cuda.current_stream().cuda_stream
         self.native.execute_many([t.data_ptr() for t in src_tensors],
                                  [t.data_ptr() for t in dst_tensors], stream)
+        if sync:
+            self.native.wait(stream)
+
+
+class NativeSoaTransposition(NativeMultiTransposition):
+    """GPU execution of one SplitTransposition or JoinTransposition: the
+    ordinary scalar native plan, the ``n``-field staging and the communicator
+    of a MultiTransposition over the scalar fields, run with the
+    vector-valued array on one side (pa_transpose_execute_split / _join)."""
+
+    def __init__(self, t):
+        plan, f0 = t.plan, t.fields[0]
+        self._setup(NativePlan(plan.Pi, plan.Po, plan.rank,
+                               f0.data.element_size(), plan.extra_dims),
+                    plan, t.n, f0.data.device)
+        self.split = t.split
+
+    def execute(self, aos_tensor, field_tensors, sync: bool = True):
+        torch = self.torch
+        for t in [aos_tensor] + list(field_tensors):
+            assert t.is_cuda and t.is_contiguous()
+        if self._pool is not None and \
+                self._pool.version != self._pool_version:
+            self._bind_pool()  # another plan grew the pool: re-point
+        stream = torch.cuda.current_stream().cuda_stream
+        ptrs = [t.data_ptr() for t in field_tensors]
+        if self.split:
+            self.native.execute_split(aos_tensor.data_ptr(), ptrs, stream)
+        else:
+            self.native.execute_join(ptrs, aos_tensor.data_ptr(), stream)
         if sync:
             self.native.wait(stream)

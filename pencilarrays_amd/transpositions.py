@@ -25,7 +25,8 @@ from typing import Callable, NamedTuple, Optional, Sequence
 import numpy as np
 
 from .array import PencilArray
-from .copyexec import apply_copy, apply_copy_conv, apply_fill
+from .copyexec import (apply_copy, apply_copy_conv, apply_copy_soa,
+                       apply_fill)
 from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
                    peer_message, stage_descs)
@@ -475,6 +476,164 @@ def transpose_many_into(dests: Sequence[PencilArray],
                               scale=scale).execute()
 
 
+def _check_soa(aos: PencilArray, fields: Sequence[PencilArray]) -> int:
+    """Validate the two sides of a split or join transpose (ValueError) and
+    return ``n``: ``aos`` is the vector-valued array, ``fields`` its ``n``
+    scalar fields on the other pencil."""
+    fields = list(fields)
+    n = len(fields)
+    if n < 2:
+        raise ValueError(
+            f"a split or join transpose needs at least 2 fields (got {n})")
+    if aos.ncomp != n or not aos.elem_dims:
+        raise ValueError(
+            f"the vector-valued array has {aos.ncomp} scalars per element "
+            f"(elem_dims {aos.elem_dims}) for {n} fields")
+    f0 = fields[0]
+
+    def storage(a):
+        if a.is_torch:
+            return ("torch", a.data.dtype, str(a.data.device))
+        return ("numpy", a.data.dtype, "cpu")
+
+    def same_pencil(a, b):
+        return (tuple(a.topology.dims) == tuple(b.topology.dims)
+                and tuple(a.size_global) == tuple(b.size_global)
+                and tuple(a.decomp_dims) == tuple(b.decomp_dims)
+                and tuple(a.perm) == tuple(b.perm))
+
+    for i, f in enumerate(fields):
+        if f.elem_dims:
+            raise ValueError(
+                f"field {i}: a scalar field cannot have elem_dims "
+                f"{f.elem_dims}")
+        if f.extra_dims != aos.extra_dims:
+            raise ValueError(
+                f"field {i}: incompatible extra dimensions of PencilArrays: "
+                f"{f.extra_dims} != {aos.extra_dims}")
+        if f.rank != aos.rank:
+            raise ValueError(
+                f"field {i}: every array must live on the same rank")
+        if not same_pencil(f.pencil, f0.pencil):
+            raise ValueError(f"field {i}: pencil differs from field 0's")
+        if storage(f) != storage(aos):
+            raise ValueError(
+                f"field {i}: the scalar dtype, backend and device must be "
+                f"the same on both sides: {storage(f)} != {storage(aos)}")
+        if _arrays_alias(f.data, aos.data) or any(
+                _arrays_alias(f.data, g.data) for g in fields[:i]):
+            raise ValueError(
+                f"field {i}: a split or join transpose cannot run in place: "
+                f"the arrays must not alias")
+    if aos.data.dtype.itemsize not in (4, 8, 16):
+        raise ValueError(
+            f"a split or join transpose moves scalars of 4, 8 or 16 bytes, "
+            f"not {aos.data.dtype}")
+    return n
+
+
+class _SoaTransposition:
+    """What SplitTransposition and JoinTransposition share: ``aos`` is the
+    vector-valued array, ``fields`` the scalar ones."""
+
+    split: bool
+
+    def __init__(self, aos: PencilArray, fields: Sequence[PencilArray]):
+        self.aos, self.fields = aos, list(fields)
+        self.n = _check_soa(aos, self.fields)
+        f0 = self.fields[0]
+        Pi, Po = (aos.pencil, f0.pencil) if self.split else \
+            (f0.pencil, aos.pencil)
+        self.plan: TransposePlan = build_plan(Pi, Po, aos.rank,
+                                              aos.extra_dims)
+        self._native = None
+
+    def _component(self, c: int) -> PencilArray:
+        """Component ``c`` of the vector-valued array as a scalar array of
+        its own (numpy)."""
+        a = self.aos
+        return PencilArray(a.pencil, a.rank,
+                           np.ascontiguousarray(a.data.reshape(-1, self.n)[:, c]),
+                           a.extra_dims)
+
+    def _execute_numpy(self):
+        # the host mirror pins the semantics, not the performance: one
+        # single-field Transposition per component
+        if self.split:
+            for c, f in enumerate(self.fields):
+                Transposition(f, self._component(c)).execute()
+        else:
+            for c, f in enumerate(self.fields):
+                tmp = self._component(c)
+                Transposition(tmp, f).execute()
+                self.aos.data.reshape(-1, self.n)[:, c] = tmp.data
+
+    def execute(self, sync: bool = True):
+        """Run the transpose; ``sync=False`` returns with the work enqueued
+        (see :meth:`Transposition.execute`)."""
+        if self.aos.is_torch:
+            if not self.aos.data.is_cuda:
+                raise RuntimeError(
+                    "torch CPU tensors are not a supported backend: use "
+                    "numpy arrays for the CPU host mirror, or cuda tensors "
+                    "for the native engine")
+            from . import native
+            if self._native is None:
+                self._native = native.NativeSoaTransposition(self)
+            self._native.execute(self.aos.data,
+                                 [f.data for f in self.fields], sync=sync)
+        else:
+            self._execute_numpy()
+        return self.fields if self.split else self.aos
+
+    def wait(self):
+        """MPI.Waitall(t) (Transpositions.jl:128-131)."""
+        if self._native is not None:
+            import torch
+            self._native.native.wait(torch.cuda.current_stream().cuda_stream)
+        return self
+
+
+class SplitTransposition(_SoaTransposition):
+    """``SplitTransposition(dests, src)``: the transpose that reads a
+    vector-valued array writes scalar fields.  ``src`` has ``elem_dims`` of
+    product ``n = len(dests)`` on the input pencil, every ``dests[c]`` is a
+    scalar array of the same dtype on the output pencil, and
+    ``dests[c] == T(src[c])`` bit for bit, component ``c`` being flat
+    position ``c`` inside the element (pa_transpose_execute_split).  The
+    layout change rides in the pack and the local copy; staging and messages
+    are those of ``MultiTransposition`` on the component copies."""
+
+    split = True
+
+    def __init__(self, dests: Sequence[PencilArray], src: PencilArray):
+        super().__init__(src, dests)
+        self.src, self.dests = src, self.fields
+
+
+class JoinTransposition(_SoaTransposition):
+    """``JoinTransposition(dest, srcs)``: the transpose that reads scalar
+    fields writes the vector-valued array, ``dest[c] == T(srcs[c])`` bit for
+    bit (pa_transpose_execute_join).  The layout change rides in the local
+    copy and the unpack; see :class:`SplitTransposition`."""
+
+    split = False
+
+    def __init__(self, dest: PencilArray, srcs: Sequence[PencilArray]):
+        super().__init__(dest, srcs)
+        self.dest, self.srcs = dest, self.fields
+
+
+def transpose_split_into(dests: Sequence[PencilArray], src: PencilArray):
+    """Split transpose ``dests[c] <- src[c]`` in one call."""
+    return SplitTransposition(dests, src).execute()
+
+
+def transpose_join_into(dest: PencilArray, srcs: Sequence[PencilArray]):
+    """Join transpose ``dest[c] <- srcs[c]`` in one call."""
+    return JoinTransposition(dest, srcs).execute()
+
+
 # ----------------------------------------------------------------------
 # In-process multi-rank simulation (test harness only): runs every rank's
 # pack/exchange/unpack inside one process, memcpy standing in for the
@@ -585,3 +744,115 @@ def run_transpose_sim_many(dests_per_rank: Sequence[Sequence[PencilArray]],
     if staging_out is not None:
         staging_out["send"] = send_bufs
         staging_out["recv"] = recv_bufs
+
+
+SIM_STAGES = ("pack", "exchange", "local", "unpack")
+
+
+def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
+                 fields_per_rank: Sequence[Sequence[PencilArray]],
+                 staging_out=None, stages=SIM_STAGES,
+                 staging_in=None) -> None:
+    """The multi-rank simulation of a split (``aos`` on the source pencil) or
+    join (``aos`` on the destination pencil) transpose: the stages and the
+    n-field staging layout of :func:`run_transpose_sim_many`, with the
+    descriptors of one scalar component applied to the vector-valued side
+    through ``apply_copy_soa``.  ``stages`` names the stages to run and
+    ``staging_in`` supplies ``send`` / ``recv`` buffers, so that one side of
+    a hop can be run by the ordinary n-field stages."""
+    unknown = set(stages) - set(SIM_STAGES)
+    if unknown:
+        raise ValueError(f"unknown stages {sorted(unknown)}")
+    pack, local = "pack" in stages, "local" in stages
+    exchange, unpack = "exchange" in stages, "unpack" in stages
+    nranks = len(aos_per_rank)
+    n = _check_soa(aos_per_rank[0], fields_per_rank[0])
+    plans = []
+    for r in range(nranks):
+        a, fs = aos_per_rank[r], fields_per_rank[r]
+        if _check_soa(a, fs) != n:
+            raise ValueError("every rank needs the same number of fields")
+        Pi, Po = (a.pencil, fs[0].pencil) if split else \
+            (fs[0].pencil, a.pencil)
+        plans.append(build_plan(Pi, Po, r, a.extra_dims))
+    dt = aos_per_rank[0].data.dtype
+    if staging_in is not None:
+        send_bufs, recv_bufs = staging_in["send"], staging_in["recv"]
+    else:
+        send_bufs, recv_bufs = [], []
+        for p in plans:
+            ns, nr = buffer_nelem_many(p, n)
+            send_bufs.append(np.empty(ns, dtype=dt))
+            recv_bufs.append(np.empty(nr, dtype=dt))
+
+    for r, p in enumerate(plans):
+        aos, fs = aos_per_rank[r].data, fields_per_rank[r]
+        for c in range(n):
+            if pack:
+                for which, d in stage_descs(p, n, c, 0):
+                    assert which == 1, "a split or join plan is not aliased"
+                    if split:
+                        apply_copy_soa(d, aos, send_bufs[r], n, c, True)
+                    else:
+                        apply_copy(d, fs[c].data, send_bufs[r])
+            if local:
+                for which, d in stage_descs(p, n, c, 1):
+                    assert which == 0, "a split or join plan is not aliased"
+                    apply_copy_soa(d, aos, fs[c].data, n, c, split)
+
+    # exchange: ONE slice copy per peer pair, all n components in it
+    if exchange:
+        for r, p in enumerate(plans):
+            if p.r_dim is None:
+                continue
+            for blk in p.peers:
+                if blk.peer_k == p.my_k or blk.send_nelem == 0:
+                    continue
+                so, sn, _, _ = peer_message(p, n, blk.peer_k)
+                q = plans[blk.global_rank]
+                _, _, ro, rn = peer_message(q, n, p.my_k)
+                assert rn == sn, (r, blk.peer_k, sn, rn)
+                recv_bufs[blk.global_rank][ro:ro + rn] = \
+                    send_bufs[r][so:so + sn]
+
+    if unpack:
+        for r, p in enumerate(plans):
+            aos, fs = aos_per_rank[r].data, fields_per_rank[r]
+            for c in range(n):
+                for which, d in stage_descs(p, n, c, 2):
+                    if split:
+                        apply_copy(d, recv_bufs[r], fs[c].data)
+                    else:
+                        apply_copy_soa(d, aos, recv_bufs[r], n, c, False)
+    if staging_out is not None:
+        staging_out["send"] = send_bufs
+        staging_out["recv"] = recv_bufs
+
+
+def run_transpose_sim_split(dests_per_rank: Sequence[Sequence[PencilArray]],
+                            srcs: Sequence[PencilArray],
+                            staging_out=None, stages=SIM_STAGES,
+                            staging_in=None) -> None:
+    """Every rank's split transpose ``dests_per_rank[r][c] <- srcs[r][c]``
+    (:class:`SplitTransposition`) with the n-field staging layout of
+    :func:`run_transpose_sim_many`: the pack reads the vector-valued source
+    and fills the ``n`` component slots of every send block, the exchange is
+    one slice copy per peer pair, the unpack is the ordinary n-field one.
+    ``staging_out``, if a dict, receives the ``send`` / ``recv`` buffers per
+    rank, in scalars.  ``stages`` (a subset of ``SIM_STAGES``) runs only
+    those stages, on the buffers of ``staging_in`` if given: the way to put
+    an ordinary n-field stage on the other side of a hop."""
+    _run_sim_soa(True, srcs, dests_per_rank, staging_out, stages, staging_in)
+
+
+def run_transpose_sim_join(dests: Sequence[PencilArray],
+                           srcs_per_rank: Sequence[Sequence[PencilArray]],
+                           staging_out=None, stages=SIM_STAGES,
+                           staging_in=None) -> None:
+    """Every rank's join transpose ``dests[r][c] <- srcs_per_rank[r][c]``
+    (:class:`JoinTransposition`): the ordinary n-field pack, one slice copy
+    per peer pair, and an unpack that writes the vector-valued destination
+    from the ``n`` component slots of every recv block.  ``staging_out``,
+    ``stages`` and ``staging_in`` as in :func:`run_transpose_sim_split`."""
+    _run_sim_soa(False, dests, srcs_per_rank, staging_out, stages,
+                 staging_in)
