@@ -1,7 +1,9 @@
-"""Helpers shared by the truncated-transpose tests.  Nothing here uses the
-plan code under test: the keep set becomes a numpy boolean mask over the
-global index space, ownership comes from the oracle's ``owned_region``, and
-the expected destinations are the C oracle run on the masked input."""
+"""Helpers shared by the truncated-transpose tests.  No expected value here
+uses the plan code under test: the keep set becomes a numpy boolean mask over
+the global index space, ownership comes from the oracle's ``owned_region``,
+and the expected destinations are the C oracle run on the masked input.  The
+expected launch rows at the end restate the grouping rules over the Python
+plan's descriptors and the per-descriptor host queries."""
 
 from __future__ import annotations
 
@@ -10,7 +12,9 @@ import math
 import numpy as np
 
 import oracle as orc
-from many_util import _oracle
+from many_util import _oracle, ceil_div, expected_workgroups
+from pencilarrays_amd import native
+from pencilarrays_amd.plan import stage_descs
 
 ID3 = (0, 1, 2)
 ID4 = (0, 1, 2, 3)
@@ -148,3 +152,77 @@ def expected_keep(parents, cfg, esz, keep, oracle_lib_path, fill_zero=True,
                 e[~dmask[r]] = sentinel
         out.append(exp)
     return out
+
+
+# ---- expected launch rows of ordinary and keep plans (host queries) -----
+
+def _tup(d):
+    return (d.dims, d.sstrides, d.soffset, d.dstrides, d.doffset)
+
+
+def _wg(desc, kk, ssz, ncomp):
+    """Workgroups by the documented grid rules, None where the kind has
+    none restated in the tests."""
+    if kk.byteified:
+        return None
+    if kk.kind == native.KERNEL_GENERIC:
+        return min(ceil_div(math.prod(desc[0]), 256), 8192)
+    if kk.kind in (native.KERNEL_COPY_1D, native.KERNEL_LINEAR,
+                   native.KERNEL_TILE, native.KERNEL_TILE_VS,
+                   native.KERNEL_TILE_PK, native.KERNEL_TILE_WIDE):
+        return expected_workgroups(desc, kk, ssz, ncomp)
+    return None
+
+
+def expected_rows(pl, n, stage, ssz, ncomp, sp, dp, send, recv):
+    """The rows pa_plan_stage_launches must report, from the Python plan's
+    sub-box tables and the per-descriptor queries with the real pointers:
+    linear-family entries of one word share a grouped row, TILE / TILE_VS at
+    sweep 1 likewise, anything else is a row of its own; the fill entries of
+    every field share ONE grouped row at the end of the local stage.
+    ``workgroups`` is None where it is not checked."""
+    rows = []   # [kind, grouped, entries, workgroups, word]
+
+    def add(kind, grouped, wg, word):
+        if grouped:
+            for r in rows:
+                if r[1] and r[0] == kind and r[4] == word:
+                    r[2] += 1
+                    r[3] = None if wg is None or r[3] is None else r[3] + wg
+                    return
+        rows.append([kind, grouped, 1, wg, word])
+
+    for f in range(n):
+        for which, d in stage_descs(pl, n, f, stage):
+            src = sp[f] if which in (0, 1, 3) else recv
+            dst = {1: send, 3: recv}.get(which, dp[f] if dp else 0)
+            kk = native.copy_kernel_kind(d, ssz, src, dst, ncomp)
+            wg = _wg(_tup(d), kk, ssz, ncomp)
+            if kk.kind in (native.KERNEL_COPY_1D, native.KERNEL_LINEAR):
+                add(native.KERNEL_LINEAR, True, wg, kk.word_bytes)
+            elif kk.kind in (native.KERNEL_TILE, native.KERNEL_TILE_VS) \
+                    and kk.sweep_depth == 1:
+                add(kk.kind, True, wg, kk.word_bytes)
+            else:
+                add(kk.kind, False, wg, kk.word_bytes)
+    if stage == native.STAGE_LOCAL:
+        for f in range(n):
+            for fd in pl.fills:
+                fk = native.fill_kernel_kind(fd, ssz, dp[f], ncomp)
+                assert fk.kind == native.KERNEL_FILL
+                lanes = (fd.nelem * ssz * ncomp // fk.store_bytes
+                         if fd.dstrides[0] == 1 else fd.nelem)
+                add(native.KERNEL_FILL, True, ceil_div(lanes, 256), 0)
+    return rows
+
+
+def check_rows(p, pl, n, ssz, ncomp, sp, dp, send, recv):
+    for stage in (native.STAGE_PACK, native.STAGE_LOCAL, native.STAGE_UNPACK):
+        got = p.stage_launches(n, stage, sp, dp)
+        want = expected_rows(pl, n, stage, ssz, ncomp, sp, dp, send, recv)
+        assert [(l.kind, l.grouped, l.entries) for l in got] == \
+            [(w[0], w[1], w[2]) for w in want], (stage, got, want)
+        for l, w in zip(got, want):
+            if w[3] is not None:
+                assert l.workgroups == w[3], (stage, l, w)
+    return p.stage_launches(n, native.STAGE_LOCAL, sp, dp)

@@ -1,9 +1,12 @@
 """Property fuzz on the GPU: seeded-random world-1 transpose configurations
 through the REAL engine (pa_transpose_execute on device) vs the independent
 direct-spec oracle, bit-exact, with sentinel-filled destinations and
-round-trip identity.  Covers random shape/permutation/dtype mixes across
-every kernel path the dispatcher can pick (vector-store tile, scalar tile,
-linear runs, 1-D copy incl. the NT gate, byte-ified odd sizes)."""
+round-trip identity.  Covers random shape/permutation/dtype mixes of 2-D to
+4-D arrays on ONE rank (``pdims`` all 1), one field, five float dtypes,
+``Transposition`` without options, out of place and in place: the plain
+copy kernels such shapes select.  The plan flavours (n fields, elem_dims,
+keep, wire, scale, split and join) and process grids of several ranks are
+fuzzed in test_gpu_fuzz_multirank.py."""
 
 import math
 import os
