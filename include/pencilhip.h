@@ -456,7 +456,40 @@ int64_t pa_plan_stage_table_builds(const pa_plan *p);
  * pa_transpose_wait and pa_plan_stage_times work after them.
  * Refused with an error: a PA_PLAN_ALIASED plan (the two sides have different
  * element sizes and cannot alias), a keep plan, a wire plan, a plan with a
- * scale set, a composite plan (ncomp > 1), n < 2, S not 4, 8 or 16. */
+ * scale set, a composite plan (ncomp > 1), n < 2, S not 4, 8 or 16.
+ *
+ * A scale is given PER CALL, to the *_scaled forms below, exactly as n is: the
+ * plan stays the ordinary scalar plan, because a plan on which
+ * pa_plan_set_scale was called is refused by every split / join call, plain
+ * or scaled (its scale names the stages of an ordinary transpose, which are
+ * not the ones a split multiplies in).  R = scalar is PA_SCALAR_F32 or
+ * PA_SCALAR_F64 and S must be one or two R: (S, R) = (4, F32), (8, F32)
+ * (complex64), (8, F64) or (16, F64) (complex128).  With a = R(alpha) rounded
+ * to nearest even and (*) ONE IEEE multiply per real scalar (round to nearest
+ * even, subnormals kept, a complex scalar component by component), the
+ * contract of pa_plan_set_scale:
+ *     split:  F_c == T(A[c] (*) a)      join:  A[c] == T(F_c (*) a)
+ * bit for bit on every non-NaN scalar (a NaN stays NaN, sign and payload
+ * unspecified), whatever the process grid; every scalar is multiplied exactly
+ * once, in the two stages that carry the layout change:
+ *   join   local_join and unpack_join multiply, the destination side as in a
+ *          scaled plan.  The pack is pa_transpose_pack_many: staging and
+ *          messages carry UNSCALED bytes, identical to the plain join's.
+ *   split  pack_split and local_split multiply, the SOURCE side, because the
+ *          split's unpack is the ordinary pa_transpose_unpack_many of an
+ *          ordinary plan and cannot multiply.  Staging and messages therefore
+ *          carry SCALED bytes: those of the n-field plan applied to the scaled
+ *          component copies A[c] (*) a, and a peer that unpacks with the
+ *          ordinary n-field stage receives the scaled fields.
+ * alpha == 1.0 means "no scale": the call runs exactly the code of the plain
+ * call, NaN payloads included.  alpha is a kernel argument: calls with
+ * different alpha on one plan build and allocate nothing.  The kernel
+ * selection is that of the plain calls, unchanged (pa_copy_kernel_kind_soa
+ * reports kind, V and tile shape for both); the scaled call launches the
+ * scaling form of the selected kernel.
+ * Errors, raised before any pointer is touched: everything the plain calls
+ * refuse, with their messages; then an unknown scalar code, a NaN or infinite
+ * alpha, an (S, R) pair outside the four above. */
 pa_status pa_transpose_pack_split(pa_plan *p, int n, const void *src_aos,
                                   void *stream);
 pa_status pa_transpose_local_split(pa_plan *p, int n, const void *src_aos,
@@ -470,6 +503,27 @@ pa_status pa_transpose_execute_split(pa_plan *p, int n, const void *src_aos,
 pa_status pa_transpose_execute_join(pa_plan *p, int n,
                                     const void *const *srcs, void *dst_aos,
                                     void *stream);
+pa_status pa_transpose_pack_split_scaled(pa_plan *p, int n, int scalar,
+                                         double alpha, const void *src_aos,
+                                         void *stream);
+pa_status pa_transpose_local_split_scaled(pa_plan *p, int n, int scalar,
+                                          double alpha, const void *src_aos,
+                                          void *const *dsts, void *stream);
+pa_status pa_transpose_local_join_scaled(pa_plan *p, int n, int scalar,
+                                         double alpha,
+                                         const void *const *srcs,
+                                         void *dst_aos, void *stream);
+pa_status pa_transpose_unpack_join_scaled(pa_plan *p, int n, int scalar,
+                                          double alpha, void *dst_aos,
+                                          void *stream);
+pa_status pa_transpose_execute_split_scaled(pa_plan *p, int n, int scalar,
+                                            double alpha,
+                                            const void *src_aos,
+                                            void *const *dsts, void *stream);
+pa_status pa_transpose_execute_join_scaled(pa_plan *p, int n, int scalar,
+                                           double alpha,
+                                           const void *const *srcs,
+                                           void *dst_aos, void *stream);
 
 /* ---- reductions (src/reductions.jl:9-38) ----------------------------- */
 /* One ncclAllReduce over a communicator (normally the FULL topology comm):
@@ -658,6 +712,21 @@ pa_status pa_device_copy_soa(int nd, const int64_t *dims, const int64_t *sstr,
                              int64_t soff, const int64_t *dstr, int64_t doff,
                              int64_t scalar_size, int n, int dir, void *aos,
                              void *const *fields, void *stream);
+/* The same copy with every real scalar multiplied once by a = R(alpha), in
+ * registers between the load and the store (the kernel body a *_scaled split
+ * or join stage runs): fields[c][..] = aos[..] (*) a, or the reverse.
+ * scalar = R is PA_SCALAR_F32 or PA_SCALAR_F64 and scalar_size one or two R.
+ * The kernel, V and tile shape are those pa_copy_kernel_kind_soa reports for
+ * the plain copy: there is no selection of its own.  Always runs the scaling
+ * kernel, alpha == 1.0 included, as pa_device_copy_scale does.  Errors beyond
+ * pa_device_copy_soa's: an unknown scalar code, a NaN or infinite alpha, a
+ * scalar_size that is neither one nor two R. */
+pa_status pa_device_copy_soa_scale(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int64_t scalar_size, int n, int dir,
+                                   int scalar, double alpha, void *aos,
+                                   void *const *fields, void *stream);
 /* Which split / join kernel runs for this descriptor (host-only; the n + 1
  * pointers are used for their alignment only, and fields may be NULL, taken
  * as aligned).  out = {kind, V, tile_i, tile_j, sweep_depth}:

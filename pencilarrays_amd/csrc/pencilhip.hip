@@ -1243,7 +1243,40 @@ __global__ __launch_bounds__(256) void k_scale_generic(
 #define PA_SOA_TILE_MAX_N 4
 #define PA_SOA_TILE_TJ 16
 #define PA_SOA_GENERIC_PTRS 8
-template <int N> struct SoaPtrs { void *p[N]; };
+/* Multiplier policy of the split / join kernels, applied to every scalar
+ * word while it sits in a register.  SoaNoMul is the identity: the plain
+ * kernels.  SoaMul<R> is the scale of the *_scaled calls: the word is one or
+ * two real scalars R (float or double; two make a complex scalar) and every
+ * one of them is multiplied once by a, the x * a of scale_linear_body.  The
+ * policy is a base of the field pointers and travels with them by value: an
+ * empty one leaves the kernel arguments as they were.  The index arithmetic,
+ * the grid split and the addressing of a kernel are the same lines under
+ * either policy. */
+struct SoaNoMul {
+    /* static and by reference: the word the caller names, not a copy of it,
+     * and no use of the pointer struct's address */
+    template <typename W>
+    static __device__ __forceinline__ const W &mul(const W &x)
+    {
+        return x;
+    }
+};
+template <typename R> struct SoaMul {
+    R a;
+    template <typename W> __device__ __forceinline__ W mul(W x) const
+    {
+        constexpr int L = (int)(sizeof(W) / sizeof(R));
+        static_assert(sizeof(W) == L * sizeof(R) && (L == 1 || L == 2),
+                      "a scalar word is one or two real scalars");
+        VecT<R, L> r;
+        __builtin_memcpy(&r, &x, sizeof(W));
+#pragma unroll
+        for (int k = 0; k < L; k++) r.v[k] = r.v[k] * a;
+        __builtin_memcpy(&x, &r, sizeof(W));
+        return x;
+    }
+};
+template <int N, typename M = SoaNoMul> struct SoaPtrs : M { void *p[N]; };
 
 /* Axis 0 contiguous on both sides.  A lane owns V consecutive elements: the
  * N*V AoS scalars are N aligned V-scalar vectors next to each other, and each
@@ -1251,9 +1284,10 @@ template <int N> struct SoaPtrs { void *p[N]; };
  * registers with compile-time indices.  The descriptor is in units of V
  * scalars.  The N AoS accesses of a wave cover one contiguous range of
  * 64*N*V scalars, every byte of it exactly once. */
-template <typename S, int DIR, int N, int V>
+template <typename S, int DIR, int N, int V, typename M = SoaNoMul>
 __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
-                                                    SoaPtrs<N> f, DescDev d)
+                                                    SoaPtrs<N, M> f,
+                                                    DescDev d)
 {
     typedef VecT<S, V> SV;
     const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
@@ -1280,6 +1314,8 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
             for (int j = 0; j < V; j++) flat[k * V + j] = in.v[j];
         }
 #pragma unroll
+        for (int k = 0; k < N * V; k++) flat[k] = f.mul(flat[k]);
+#pragma unroll
         for (int c = 0; c < N; c++) {
             SV out;
 #pragma unroll
@@ -1293,6 +1329,8 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
 #pragma unroll
             for (int v = 0; v < V; v++) flat[v * N + c] = in.v[v];
         }
+#pragma unroll
+        for (int k = 0; k < N * V; k++) flat[k] = f.mul(flat[k]);
 #pragma unroll
         for (int k = 0; k < N; k++) {
             SV out;
@@ -1321,9 +1359,9 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
  * LDS words).  The AoS store reads, at word index q = j*N + c of row i,
  * c*plane + j*pitch + i; with plane == 1 and pitch == N (mod 256/W) that is
  * q + i modulo the bank span: consecutive lanes, consecutive banks. */
-template <typename S, int DIR, int N>
+template <typename S, int DIR, int N, typename M = SoaNoMul>
 __global__ __launch_bounds__(256) void k_soa_tile(
-    void *__restrict__ aos_, SoaPtrs<N> f, DescDev d, int ta, int ti,
+    void *__restrict__ aos_, SoaPtrs<N, M> f, DescDev d, int ta, int ti,
     int pitch, int plane, int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
 {
     extern __shared__ uint4 soa_lds[];
@@ -1381,7 +1419,7 @@ __global__ __launch_bounds__(256) void k_soa_tile(
                 dst += do_b + j0 + i0 * di + j;
                 const S *tcol = tile + j * pitch + c;
                 for (int i = ty; i < ni; i += NR)
-                    dst[(int64_t)i * di] = tcol[i * N];
+                    dst[(int64_t)i * di] = f.mul(tcol[i * N]);
             }
         }
     } else {
@@ -1407,7 +1445,7 @@ __global__ __launch_bounds__(256) void k_soa_tile(
                 S *row = base + (int64_t)i * di * N;
                 for (int q = tx; q < nw; q += 64) {
                     const int j = q / N, c = q - j * N;
-                    row[q] = tile[c * plane + j * pitch + i];
+                    row[q] = f.mul(tile[c * plane + j * pitch + i]);
                 }
             }
         }
@@ -1417,10 +1455,10 @@ __global__ __launch_bounds__(256) void k_soa_tile(
 /* Any other descriptor, any n: one lane per scalar, grid-stride like
  * k_copy_generic.  blockIdx.z is the component within this launch's chunk of
  * at most PA_SOA_GENERIC_PTRS fields, whose first component is c0. */
-template <typename S, int DIR>
+template <typename S, int DIR, typename M = SoaNoMul>
 __global__ __launch_bounds__(256) void k_soa_generic(
-    void *__restrict__ aos_, SoaPtrs<PA_SOA_GENERIC_PTRS> f, DescDev d, int n,
-    int c0)
+    void *__restrict__ aos_, SoaPtrs<PA_SOA_GENERIC_PTRS, M> f, DescDev d,
+    int n, int c0)
 {
     const int c = blockIdx.z;
     S *fp = (S *)f.p[0];
@@ -1439,9 +1477,9 @@ __global__ __launch_bounds__(256) void k_soa_generic(
             doo += j * d.dstr[a];
         }
         if (DIR == PA_SOA_SPLIT)
-            fp[doo] = aos[so * n];
+            fp[doo] = f.mul(aos[so * n]);
         else
-            aos[doo * n] = fp[so];
+            aos[doo * n] = f.mul(fp[so]);
     }
 }
 
@@ -2613,11 +2651,16 @@ static pa_status select_kernel_soa(const CopyDescH &dn, int64_t ssz, int n,
     return 0;
 }
 
-template <typename S, int DIR, int N>
+/* M is the multiplier policy: SoaNoMul for a plain call, SoaMul<R> holding
+ * a = R(alpha) for a scaled one, S being one or two R.  It picks the
+ * instantiation and rides in the pointer struct; everything else about the
+ * launch is the same code for both. */
+template <typename S, typename M, int DIR, int N>
 static pa_status launch_soa_n(const SoaSel &k, void *aos, void *const *fields,
-                              hipStream_t stream)
+                              const M &m, hipStream_t stream)
 {
-    SoaPtrs<N> f;
+    SoaPtrs<N, M> f;
+    static_cast<M &>(f) = m;
     for (int c = 0; c < N; c++) f.p[c] = fields[c];
     DescDev dd = to_dev(k.d);
     dim3 grid;
@@ -2626,7 +2669,7 @@ static pa_status launch_soa_n(const SoaSel &k, void *aos, void *const *fields,
             return gst;
         constexpr int VMAX = 16 / (int)sizeof(S);
 #define SOA_LIN(VV)                                                          \
-    hipLaunchKernelGGL((k_soa_linear<S, DIR, N, VV>), grid, dim3(256), 0,    \
+    hipLaunchKernelGGL((k_soa_linear<S, DIR, N, VV, M>), grid, dim3(256), 0, \
                        stream, aos, f, dd)
         if (k.V < 1 || k.V > VMAX) return fail("bad vector width %d", k.V);
         if constexpr (VMAX >= 4) {
@@ -2658,15 +2701,15 @@ static pa_status launch_soa_n(const SoaSel &k, void *aos, void *const *fields,
                                         : (size_t)N * k.plane);
     if (lds > (64u << 10))
         return fail("split/join tile needs %zu B of LDS", lds);
-    hipLaunchKernelGGL((k_soa_tile<S, DIR, N>), grid, dim3(64, 4), lds,
+    hipLaunchKernelGGL((k_soa_tile<S, DIR, N, M>), grid, dim3(64, 4), lds,
                        stream, aos, f, dd, k.ta, k.ti, k.pitch, k.plane, nti,
                        ntj, nblocks);
     return 0;
 }
 
-template <typename S, int DIR>
+template <typename S, typename M, int DIR>
 static pa_status launch_soa_t(const SoaSel &k, void *aos, void *const *fields,
-                              hipStream_t stream)
+                              const M &m, hipStream_t stream)
 {
     if (k.kind == PA_KERNEL_SOA_GENERIC) {
         /* grid-stride kernel, at most PA_SOA_GENERIC_PTRS fields a launch */
@@ -2674,42 +2717,66 @@ static pa_status launch_soa_t(const SoaSel &k, void *aos, void *const *fields,
         const int gx = grid_for(k.d.total, 256);
         for (int c0 = 0; c0 < k.n; c0 += PA_SOA_GENERIC_PTRS) {
             const int nc = std::min(k.n - c0, PA_SOA_GENERIC_PTRS);
-            SoaPtrs<PA_SOA_GENERIC_PTRS> f;
+            SoaPtrs<PA_SOA_GENERIC_PTRS, M> f;
+            static_cast<M &>(f) = m;
             for (int c = 0; c < PA_SOA_GENERIC_PTRS; c++)
                 f.p[c] = c < nc ? fields[c0 + c] : nullptr;
-            hipLaunchKernelGGL((k_soa_generic<S, DIR>), dim3(gx, 1, nc),
+            hipLaunchKernelGGL((k_soa_generic<S, DIR, M>), dim3(gx, 1, nc),
                                dim3(256), 0, stream, aos, f, dd, k.n, c0);
         }
         return 0;
     }
     switch (k.n) {
-    case 2: return launch_soa_n<S, DIR, 2>(k, aos, fields, stream);
-    case 3: return launch_soa_n<S, DIR, 3>(k, aos, fields, stream);
-    case 4: return launch_soa_n<S, DIR, 4>(k, aos, fields, stream);
+    case 2: return launch_soa_n<S, M, DIR, 2>(k, aos, fields, m, stream);
+    case 3: return launch_soa_n<S, M, DIR, 3>(k, aos, fields, m, stream);
+    case 4: return launch_soa_n<S, M, DIR, 4>(k, aos, fields, m, stream);
     default: return fail("bad split/join selection: n = %d", k.n);
     }
 }
 
-/* aos is the source of a split and the destination of a join */
+/* The scalar sizes a scale of real type `scalar` applies to: one scalar or
+ * two (a complex scalar), nothing else. */
+static pa_status check_soa_scale(int64_t ssz, int scalar, double alpha)
+{
+    if (pa_status st = check_scale(scalar, 1, alpha)) return st;
+    const int64_t sz = scalar_bytes(scalar);
+    if (ssz != sz && ssz != 2 * sz)
+        return fail("a %lld-byte scalar is neither one nor two of the "
+                    "%lld-byte real scalars of the scale",
+                    (long long)ssz, (long long)sz);
+    return 0;
+}
+
+/* aos is the source of a split and the destination of a join; scalar is the
+ * PA_SCALAR_* code of a scaling launch by alpha, or 0 for a plain one */
 static pa_status launch_soa_sel(const SoaSel &k, void *aos,
-                                void *const *fields, hipStream_t stream)
+                                void *const *fields, int scalar, double alpha,
+                                hipStream_t stream)
 {
     if (k.kind == PA_KERNEL_NONE) return 0;
     if (k.kind != PA_KERNEL_SOA_LINEAR && k.kind != PA_KERNEL_SOA_TILE &&
         k.kind != PA_KERNEL_SOA_GENERIC)
         return fail("bad split/join kernel kind %d", k.kind);
+    if (scalar)
+        if (pa_status st = check_soa_scale(k.ssz, scalar, alpha)) return st;
     pa_status st;
-#define SOA_DIR(S)                                                           \
-    (k.dir == PA_SOA_SPLIT ? launch_soa_t<S, PA_SOA_SPLIT>(k, aos, fields,   \
-                                                           stream)          \
-                           : launch_soa_t<S, PA_SOA_JOIN>(k, aos, fields,    \
-                                                          stream))
+    const SoaNoMul none;
+    const SoaMul<float> mf{(float)alpha};
+    const SoaMul<double> md{alpha};
+#define SOA_DIR(S, M, m)                                                     \
+    (k.dir == PA_SOA_SPLIT                                                   \
+         ? launch_soa_t<S, M, PA_SOA_SPLIT>(k, aos, fields, m, stream)       \
+         : launch_soa_t<S, M, PA_SOA_JOIN>(k, aos, fields, m, stream))
     if (k.ssz == 4)
-        st = SOA_DIR(uint32_t);
+        st = scalar ? SOA_DIR(uint32_t, SoaMul<float>, mf)
+                    : SOA_DIR(uint32_t, SoaNoMul, none);
     else if (k.ssz == 8)
-        st = SOA_DIR(uint64_t);
+        st = scalar == PA_SCALAR_F32   ? SOA_DIR(uint64_t, SoaMul<float>, mf)
+             : scalar == PA_SCALAR_F64 ? SOA_DIR(uint64_t, SoaMul<double>, md)
+                                       : SOA_DIR(uint64_t, SoaNoMul, none);
     else if (k.ssz == 16)
-        st = SOA_DIR(uint4);
+        st = scalar ? SOA_DIR(uint4, SoaMul<double>, md)
+                    : SOA_DIR(uint4, SoaNoMul, none);
     else
         return fail("bad scalar size %d", k.ssz);
 #undef SOA_DIR
@@ -2720,12 +2787,13 @@ static pa_status launch_soa_sel(const SoaSel &k, void *aos,
 
 static pa_status launch_desc_soa(const CopyDescH &dn, int64_t ssz, int n,
                                  int dir, void *aos, void *const *fields,
-                                 hipStream_t stream)
+                                 hipStream_t stream, int scalar = 0,
+                                 double alpha = 1.0)
 {
     SoaSel k;
     if (pa_status st = select_kernel_soa(dn, ssz, n, dir, aos, fields, &k))
         return st;
-    return launch_soa_sel(k, aos, fields, stream);
+    return launch_soa_sel(k, aos, fields, scalar, alpha, stream);
 }
 
 /* ---- zero fill: descriptor, store width, launch ----------------------- */
@@ -5127,7 +5195,10 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
  * scalars per element, components fastest.  The staging layout is the
  * multi-field one with the components as fields, so the opposite side's
  * stages are pa_transpose_*_many unchanged.  One launch per block, each
- * carrying all n components. */
+ * carrying all n components.  The *_scaled calls take a scale per call (a
+ * plan with one set is refused) and launch the scaling form of the same
+ * kernels: a split multiplies in pack and local, so its staging holds scaled
+ * scalars; a join multiplies in local and unpack, so its staging does not. */
 
 static pa_status soa_check(const pa_plan *p, int n, const void *aos,
                            const void *const *fields, bool need_fields)
@@ -5165,7 +5236,8 @@ static pa_status soa_check(const pa_plan *p, int n, const void *aos,
 /* one staged block with the vector-valued array on its other side: component
  * c's slot starts c * (block count) scalars into the block */
 static pa_status soa_staged(const pa_plan *p, int n, int dir, const SubC &sb,
-                            void *aos, void *staging, hipStream_t stream)
+                            void *aos, void *staging, int scale, double alpha,
+                            hipStream_t stream)
 {
     CopyDescH d = sb.d;
     const int64_t sh = many_shift(n, 0, sb.off, sb.n);
@@ -5182,7 +5254,55 @@ static pa_status soa_staged(const pa_plan *p, int n, int dir, const SubC &sb,
     }
     for (int c = 0; c < n; c++)
         slots[c] = (char *)staging + (int64_t)c * sb.n * p->ssz;
-    return launch_desc_soa(d, p->ssz, n, dir, aos, slots, stream);
+    return launch_desc_soa(d, p->ssz, n, dir, aos, slots, stream, scale,
+                           alpha);
+}
+
+/* The scale of a *_scaled stage call, checked after soa_check() and before
+ * any pointer is touched: *scale is the PA_SCALAR_* code the launches get, 0
+ * for alpha == 1, which runs exactly the plain call's code. */
+static pa_status soa_scale(const pa_plan *p, int scalar, double alpha,
+                           int *scale)
+{
+    if (pa_status st = check_soa_scale(p->ssz, scalar, alpha)) return st;
+    *scale = alpha == 1.0 ? 0 : scalar;
+    return 0;
+}
+
+/* The four stages behind the plain and the scaled calls, arguments already
+ * checked; scale as soa_scale() returns it (0: none). */
+static pa_status soa_pack_split(pa_plan *p, int n, const void *src_aos,
+                                int scale, double alpha, hipStream_t stream)
+{
+    for (auto &b : p->peers)
+        for (auto &sb : b.pack)
+            if (pa_status st =
+                    soa_staged(p, n, PA_SOA_SPLIT, sb, (void *)src_aos,
+                               p->send_buf, scale, alpha, stream))
+                return st;
+    return 0;
+}
+
+static pa_status soa_local(pa_plan *p, int n, int dir, void *aos,
+                           void *const *fields, int scale, double alpha,
+                           hipStream_t stream)
+{
+    for (auto &sb : p->local)
+        if (pa_status st = launch_desc_soa(sb.d, p->ssz, n, dir, aos, fields,
+                                           stream, scale, alpha))
+            return st;
+    return 0;
+}
+
+static pa_status soa_unpack_join(pa_plan *p, int n, void *dst_aos, int scale,
+                                 double alpha, hipStream_t stream)
+{
+    for (auto &b : p->peers)
+        for (auto &sb : b.unpack)
+            if (pa_status st = soa_staged(p, n, PA_SOA_JOIN, sb, dst_aos,
+                                          p->recv_buf, scale, alpha, stream))
+                return st;
+    return 0;
 }
 
 extern "C" {
@@ -5200,6 +5320,25 @@ pa_status pa_device_copy_soa(int nd, const int64_t *dims, const int64_t *sstr,
     CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
     return launch_desc_soa(d, scalar_size, n, dir, aos, fields,
                            (hipStream_t)stream);
+}
+
+pa_status pa_device_copy_soa_scale(int nd, const int64_t *dims,
+                                   const int64_t *sstr, int64_t soff,
+                                   const int64_t *dstr, int64_t doff,
+                                   int64_t scalar_size, int n, int dir,
+                                   int scalar, double alpha, void *aos,
+                                   void *const *fields, void *stream)
+{
+    if (nd <= 0 || nd > MAXND) return fail("bad nd");
+    if (pa_status st = check_soa(scalar_size, n, dir)) return st;
+    if (pa_status st = check_soa_scale(scalar_size, scalar, alpha)) return st;
+    if (!aos || !fields) return fail("null pointer");
+    for (int c = 0; c < n; c++)
+        if (!fields[c]) return fail("null pointer for field %d", c);
+    CopyDescH d = normalize_desc(nd, dims, sstr, soff, dstr, doff);
+    /* always the scaling kernel, alpha == 1 included */
+    return launch_desc_soa(d, scalar_size, n, dir, aos, fields,
+                           (hipStream_t)stream, scalar, alpha);
 }
 
 pa_status pa_copy_kernel_kind_soa(int nd, const int64_t *dims,
@@ -5229,71 +5368,101 @@ pa_status pa_transpose_pack_split(pa_plan *p, int n, const void *src_aos,
                                   void *stream)
 {
     if (pa_status st = soa_check(p, n, src_aos, nullptr, false)) return st;
-    for (auto &b : p->peers)
-        for (auto &sb : b.pack)
-            if (pa_status st =
-                    soa_staged(p, n, PA_SOA_SPLIT, sb, (void *)src_aos,
-                               p->send_buf, (hipStream_t)stream))
-                return st;
-    return 0;
+    return soa_pack_split(p, n, src_aos, 0, 1.0, (hipStream_t)stream);
 }
 
 pa_status pa_transpose_local_split(pa_plan *p, int n, const void *src_aos,
                                    void *const *dsts, void *stream)
 {
     if (pa_status st = soa_check(p, n, src_aos, dsts, true)) return st;
-    for (auto &sb : p->local)
-        if (pa_status st =
-                launch_desc_soa(sb.d, p->ssz, n, PA_SOA_SPLIT,
-                                (void *)src_aos, dsts, (hipStream_t)stream))
-            return st;
-    return 0;
+    return soa_local(p, n, PA_SOA_SPLIT, (void *)src_aos, dsts, 0, 1.0,
+                     (hipStream_t)stream);
 }
 
 pa_status pa_transpose_local_join(pa_plan *p, int n, const void *const *srcs,
                                   void *dst_aos, void *stream)
 {
     if (pa_status st = soa_check(p, n, dst_aos, srcs, true)) return st;
-    for (auto &sb : p->local)
-        if (pa_status st =
-                launch_desc_soa(sb.d, p->ssz, n, PA_SOA_JOIN, dst_aos,
-                                (void *const *)srcs, (hipStream_t)stream))
-            return st;
-    return 0;
+    return soa_local(p, n, PA_SOA_JOIN, dst_aos, (void *const *)srcs, 0, 1.0,
+                     (hipStream_t)stream);
 }
 
 pa_status pa_transpose_unpack_join(pa_plan *p, int n, void *dst_aos,
                                    void *stream)
 {
     if (pa_status st = soa_check(p, n, dst_aos, nullptr, false)) return st;
-    for (auto &b : p->peers)
-        for (auto &sb : b.unpack)
-            if (pa_status st = soa_staged(p, n, PA_SOA_JOIN, sb, dst_aos,
-                                          p->recv_buf, (hipStream_t)stream))
-                return st;
-    return 0;
+    return soa_unpack_join(p, n, dst_aos, 0, 1.0, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_pack_split_scaled(pa_plan *p, int n, int scalar,
+                                         double alpha, const void *src_aos,
+                                         void *stream)
+{
+    int scale;
+    if (pa_status st = soa_check(p, n, src_aos, nullptr, false)) return st;
+    if (pa_status st = soa_scale(p, scalar, alpha, &scale)) return st;
+    return soa_pack_split(p, n, src_aos, scale, alpha, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_local_split_scaled(pa_plan *p, int n, int scalar,
+                                          double alpha, const void *src_aos,
+                                          void *const *dsts, void *stream)
+{
+    int scale;
+    if (pa_status st = soa_check(p, n, src_aos, dsts, true)) return st;
+    if (pa_status st = soa_scale(p, scalar, alpha, &scale)) return st;
+    return soa_local(p, n, PA_SOA_SPLIT, (void *)src_aos, dsts, scale, alpha,
+                     (hipStream_t)stream);
+}
+
+pa_status pa_transpose_local_join_scaled(pa_plan *p, int n, int scalar,
+                                         double alpha,
+                                         const void *const *srcs,
+                                         void *dst_aos, void *stream)
+{
+    int scale;
+    if (pa_status st = soa_check(p, n, dst_aos, srcs, true)) return st;
+    if (pa_status st = soa_scale(p, scalar, alpha, &scale)) return st;
+    return soa_local(p, n, PA_SOA_JOIN, dst_aos, (void *const *)srcs, scale,
+                     alpha, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_unpack_join_scaled(pa_plan *p, int n, int scalar,
+                                          double alpha, void *dst_aos,
+                                          void *stream)
+{
+    int scale;
+    if (pa_status st = soa_check(p, n, dst_aos, nullptr, false)) return st;
+    if (pa_status st = soa_scale(p, scalar, alpha, &scale)) return st;
+    return soa_unpack_join(p, n, dst_aos, scale, alpha, (hipStream_t)stream);
 }
 
 /* the hop shared by both: pack, the single-group exchange of
  * pa_transpose_execute_many, local, unpack; exactly one of src_aos / dst_aos
- * is set */
+ * is set.  scaled: a *_scaled call, whose scalar and alpha are checked here;
+ * a split multiplies in pack and local, a join in local and unpack. */
 static pa_status execute_soa(pa_plan *p, int n, const void *src_aos,
                              const void *const *srcs, void *dst_aos,
-                             void *const *dsts, hipStream_t stream)
+                             void *const *dsts, bool scaled, int scalar,
+                             double alpha, hipStream_t stream)
 {
     const bool split = src_aos != nullptr;
     if (pa_status st = soa_check(p, n, split ? src_aos : dst_aos,
                                  split ? (const void *const *)dsts : srcs,
                                  true))
         return st;
+    int scale = 0;
+    if (scaled)
+        if (pa_status st = soa_scale(p, scalar, alpha, &scale)) return st;
     const bool xchg = exchanging(p);
     if (xchg && !p->comm)
         return fail("subgroup exchange requires pa_plan_set_comm");
     if (pa_status st = timing_begin(p)) return st;
 
     TM_REC(0, stream);
-    if (pa_status st = split ? pa_transpose_pack_split(p, n, src_aos, stream)
-                             : pa_transpose_pack_many(p, n, srcs, stream))
+    if (pa_status st =
+            split ? soa_pack_split(p, n, src_aos, scale, alpha, stream)
+                  : pa_transpose_pack_many(p, n, srcs, stream))
         return st;
     TM_REC(1, stream);
 
@@ -5301,15 +5470,18 @@ static pa_status execute_soa(pa_plan *p, int n, const void *src_aos,
         if (pa_status st = exchange_many(p, n, stream)) return st;
 
     if (pa_status st =
-            split ? pa_transpose_local_split(p, n, src_aos, dsts, stream)
-                  : pa_transpose_local_join(p, n, srcs, dst_aos, stream))
+            split ? soa_local(p, n, PA_SOA_SPLIT, (void *)src_aos, dsts,
+                              scale, alpha, stream)
+                  : soa_local(p, n, PA_SOA_JOIN, dst_aos,
+                              (void *const *)srcs, scale, alpha, stream))
         return st;
     TM_REC(2, stream);
 
     if (xchg) HIP_CHECK(hipStreamWaitEvent(stream, p->ev_comm, 0));
     TM_REC(5, stream);
-    if (pa_status st = split ? pa_transpose_unpack_many(p, n, dsts, stream)
-                             : pa_transpose_unpack_join(p, n, dst_aos, stream))
+    if (pa_status st =
+            split ? pa_transpose_unpack_many(p, n, dsts, stream)
+                  : soa_unpack_join(p, n, dst_aos, scale, alpha, stream))
         return st;
     TM_REC(6, stream);
 #undef TM_REC
@@ -5320,7 +5492,7 @@ pa_status pa_transpose_execute_split(pa_plan *p, int n, const void *src_aos,
                                      void *const *dsts, void *stream)
 {
     if (!src_aos) return fail("null vector-valued array pointer");
-    return execute_soa(p, n, src_aos, nullptr, nullptr, dsts,
+    return execute_soa(p, n, src_aos, nullptr, nullptr, dsts, false, 0, 1.0,
                        (hipStream_t)stream);
 }
 
@@ -5329,8 +5501,28 @@ pa_status pa_transpose_execute_join(pa_plan *p, int n,
                                     void *stream)
 {
     if (!dst_aos) return fail("null vector-valued array pointer");
-    return execute_soa(p, n, nullptr, srcs, dst_aos, nullptr,
+    return execute_soa(p, n, nullptr, srcs, dst_aos, nullptr, false, 0, 1.0,
                        (hipStream_t)stream);
+}
+
+pa_status pa_transpose_execute_split_scaled(pa_plan *p, int n, int scalar,
+                                            double alpha,
+                                            const void *src_aos,
+                                            void *const *dsts, void *stream)
+{
+    if (!src_aos) return fail("null vector-valued array pointer");
+    return execute_soa(p, n, src_aos, nullptr, nullptr, dsts, true, scalar,
+                       alpha, (hipStream_t)stream);
+}
+
+pa_status pa_transpose_execute_join_scaled(pa_plan *p, int n, int scalar,
+                                           double alpha,
+                                           const void *const *srcs,
+                                           void *dst_aos, void *stream)
+{
+    if (!dst_aos) return fail("null vector-valued array pointer");
+    return execute_soa(p, n, nullptr, srcs, dst_aos, nullptr, true, scalar,
+                       alpha, (hipStream_t)stream);
 }
 
 } /* extern "C" */

@@ -321,6 +321,20 @@ def device_copy_soa(desc, scalar_size: int, n: int, direction: int,
         VP(stream)), "pa_device_copy_soa")
 
 
+def device_copy_soa_scale(desc, scalar_size: int, n: int, direction: int,
+                          scalar: int, alpha: float, aos_ptr: int, field_ptrs,
+                          stream: int = 0) -> None:
+    """Run one scaling split or join copy on the device
+    (pa_device_copy_soa_scale): every real scalar of type ``scalar`` times
+    ``S(alpha)`` on its way; the kernel is the one
+    :func:`copy_kernel_kind_soa` reports for the plain copy."""
+    lib = load()
+    args = _soa_args(desc, scalar_size, n, direction, aos_ptr, field_ptrs)
+    _check(lib, lib.pa_device_copy_soa_scale(
+        *args[:-2], int(scalar), ctypes.c_double(alpha), *args[-2:],
+        VP(stream)), "pa_device_copy_soa_scale")
+
+
 class FillKernelKind(NamedTuple):
     """pa_fill_kernel_kind: ``store_bytes`` per store of the zero fill."""
     kind: int
@@ -669,6 +683,54 @@ class NativePlan:
         _check(self.lib, self.lib.pa_transpose_execute_join(
             self._plan, n, self._ptrs(src_ptrs, n), VP(dst_aos_ptr),
             VP(stream)), "pa_transpose_execute_join")
+
+    # the same with a scale given per call: every real scalar of type
+    # ``scalar`` (SCALAR_F32 / SCALAR_F64) times ``S(alpha)``, a split in its
+    # pack and local copy, a join in its local copy and unpack
+
+    def pack_split_scaled(self, n: int, scalar: int, alpha: float,
+                          src_aos_ptr: int, stream: int = 0):
+        _check(self.lib, self.lib.pa_transpose_pack_split_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            VP(src_aos_ptr), VP(stream)), "pa_transpose_pack_split_scaled")
+
+    def local_split_scaled(self, scalar: int, alpha: float, src_aos_ptr: int,
+                           dst_ptrs, stream: int = 0):
+        n = len(dst_ptrs)
+        _check(self.lib, self.lib.pa_transpose_local_split_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            VP(src_aos_ptr), self._ptrs(dst_ptrs, n), VP(stream)),
+            "pa_transpose_local_split_scaled")
+
+    def local_join_scaled(self, scalar: int, alpha: float, src_ptrs,
+                          dst_aos_ptr: int, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_local_join_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            self._ptrs(src_ptrs, n), VP(dst_aos_ptr), VP(stream)),
+            "pa_transpose_local_join_scaled")
+
+    def unpack_join_scaled(self, n: int, scalar: int, alpha: float,
+                           dst_aos_ptr: int, stream: int = 0):
+        _check(self.lib, self.lib.pa_transpose_unpack_join_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            VP(dst_aos_ptr), VP(stream)), "pa_transpose_unpack_join_scaled")
+
+    def execute_split_scaled(self, scalar: int, alpha: float,
+                             src_aos_ptr: int, dst_ptrs, stream: int = 0):
+        n = len(dst_ptrs)
+        _check(self.lib, self.lib.pa_transpose_execute_split_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            VP(src_aos_ptr), self._ptrs(dst_ptrs, n), VP(stream)),
+            "pa_transpose_execute_split_scaled")
+
+    def execute_join_scaled(self, scalar: int, alpha: float, src_ptrs,
+                            dst_aos_ptr: int, stream: int = 0):
+        n = len(src_ptrs)
+        _check(self.lib, self.lib.pa_transpose_execute_join_scaled(
+            self._plan, n, int(scalar), ctypes.c_double(alpha),
+            self._ptrs(src_ptrs, n), VP(dst_aos_ptr), VP(stream)),
+            "pa_transpose_execute_join_scaled")
 
     def stage_table_count(self) -> int:
         """Stage tables in the plan's cache (pa_plan_stage_table_count)."""
@@ -1041,7 +1103,9 @@ class NativeSoaTransposition(NativeMultiTransposition):
     """GPU execution of one SplitTransposition or JoinTransposition: the
     ordinary scalar native plan, the ``n``-field staging and the communicator
     of a MultiTransposition over the scalar fields, run with the
-    vector-valued array on one side (pa_transpose_execute_split / _join)."""
+    vector-valued array on one side (pa_transpose_execute_split / _join).
+    A scale of the transposition goes with every call
+    (pa_transpose_execute_split_scaled / _join_scaled): the plan has none."""
 
     def __init__(self, t):
         plan, f0 = t.plan, t.fields[0]
@@ -1049,6 +1113,7 @@ class NativeSoaTransposition(NativeMultiTransposition):
                                f0.data.element_size(), plan.extra_dims),
                     plan, t.n, f0.data.device)
         self.split = t.split
+        self.scale = getattr(t, "scale", None)  # scale.Scale or None
 
     def execute(self, aos_tensor, field_tensors, sync: bool = True):
         torch = self.torch
@@ -1059,8 +1124,16 @@ class NativeSoaTransposition(NativeMultiTransposition):
             self._bind_pool()  # another plan grew the pool: re-point
         stream = torch.cuda.current_stream().cuda_stream
         ptrs = [t.data_ptr() for t in field_tensors]
-        if self.split:
+        s = self.scale
+        if self.split and s is not None:
+            self.native.execute_split_scaled(s.code, s.alpha,
+                                             aos_tensor.data_ptr(), ptrs,
+                                             stream)
+        elif self.split:
             self.native.execute_split(aos_tensor.data_ptr(), ptrs, stream)
+        elif s is not None:
+            self.native.execute_join_scaled(s.code, s.alpha, ptrs,
+                                            aos_tensor.data_ptr(), stream)
         else:
             self.native.execute_join(ptrs, aos_tensor.data_ptr(), stream)
         if sync:

@@ -31,7 +31,7 @@ from .pencil import Pencil
 from .plan import (TransposePlan, build_plan, buffer_nelem_many,
                    peer_message, stage_descs)
 from .plan import fourier_keep  # noqa: F401  (the keep-set helper, re-exported)
-from .scale import resolve_scale
+from .scale import resolve_scale, scale_array
 from .wire import narrow, resolve_wire, widen
 
 MPI_TAG = 42  # Transpositions.jl:469
@@ -538,9 +538,12 @@ class _SoaTransposition:
 
     split: bool
 
-    def __init__(self, aos: PencilArray, fields: Sequence[PencilArray]):
+    def __init__(self, aos: PencilArray, fields: Sequence[PencilArray],
+                 scale=None):
         self.aos, self.fields = aos, list(fields)
         self.n = _check_soa(aos, self.fields)
+        # scale.Scale or None; None and 1.0 give the unscaled object
+        self.scale = resolve_scale(aos.data.dtype, scale)
         f0 = self.fields[0]
         Pi, Po = (aos.pencil, f0.pencil) if self.split else \
             (f0.pencil, aos.pencil)
@@ -558,14 +561,16 @@ class _SoaTransposition:
 
     def _execute_numpy(self):
         # the host mirror pins the semantics, not the performance: one
-        # single-field Transposition per component
+        # single-field Transposition per component, which multiplies on the
+        # real view (scale.py)
+        alpha = self.scale and self.scale.alpha
         if self.split:
             for c, f in enumerate(self.fields):
-                Transposition(f, self._component(c)).execute()
+                Transposition(f, self._component(c), scale=alpha).execute()
         else:
             for c, f in enumerate(self.fields):
                 tmp = self._component(c)
-                Transposition(tmp, f).execute()
+                Transposition(tmp, f, scale=alpha).execute()
                 self.aos.data.reshape(-1, self.n)[:, c] = tmp.data
 
     def execute(self, sync: bool = True):
@@ -602,12 +607,23 @@ class SplitTransposition(_SoaTransposition):
     ``dests[c] == T(src[c])`` bit for bit, component ``c`` being flat
     position ``c`` inside the element (pa_transpose_execute_split).  The
     layout change rides in the pack and the local copy; staging and messages
-    are those of ``MultiTransposition`` on the component copies."""
+    are those of ``MultiTransposition`` on the component copies.
+
+    ``scale`` (a finite real number; ``None`` and ``1.0`` mean none) makes it
+    ``dests[c] == T(src[c] * scale)``: every real scalar of a float32 /
+    float64 / complex64 / complex128 array (a complex item is two) is
+    multiplied once by ``scale`` rounded to the scalar type, in the pack and
+    the local copy, the two stages that carry the layout change
+    (pa_transpose_execute_split_scaled).  Staging and messages therefore carry
+    the SCALED scalars, those of ``MultiTransposition`` on the scaled component
+    copies: the unpack is the ordinary one and cannot multiply.  Integer
+    arrays take no scale (``ValueError``)."""
 
     split = True
 
-    def __init__(self, dests: Sequence[PencilArray], src: PencilArray):
-        super().__init__(src, dests)
+    def __init__(self, dests: Sequence[PencilArray], src: PencilArray,
+                 scale=None):
+        super().__init__(src, dests, scale)
         self.src, self.dests = src, self.fields
 
 
@@ -615,23 +631,33 @@ class JoinTransposition(_SoaTransposition):
     """``JoinTransposition(dest, srcs)``: the transpose that reads scalar
     fields writes the vector-valued array, ``dest[c] == T(srcs[c])`` bit for
     bit (pa_transpose_execute_join).  The layout change rides in the local
-    copy and the unpack; see :class:`SplitTransposition`."""
+    copy and the unpack; see :class:`SplitTransposition`.
+
+    ``scale`` makes it ``dest[c] == T(srcs[c] * scale)``, the ``1/N`` of an
+    inverse FFT on the hop that writes the vector-valued physical-space array
+    (pa_transpose_execute_join_scaled): the multiply sits in the local copy
+    and the unpack, the destination side as in a scaled
+    :class:`Transposition`, and staging and messages carry unscaled bytes,
+    identical to the unscaled join's."""
 
     split = False
 
-    def __init__(self, dest: PencilArray, srcs: Sequence[PencilArray]):
-        super().__init__(dest, srcs)
+    def __init__(self, dest: PencilArray, srcs: Sequence[PencilArray],
+                 scale=None):
+        super().__init__(dest, srcs, scale)
         self.dest, self.srcs = dest, self.fields
 
 
-def transpose_split_into(dests: Sequence[PencilArray], src: PencilArray):
-    """Split transpose ``dests[c] <- src[c]`` in one call."""
-    return SplitTransposition(dests, src).execute()
+def transpose_split_into(dests: Sequence[PencilArray], src: PencilArray,
+                         scale=None):
+    """Split transpose ``dests[c] <- scale * src[c]`` in one call."""
+    return SplitTransposition(dests, src, scale=scale).execute()
 
 
-def transpose_join_into(dest: PencilArray, srcs: Sequence[PencilArray]):
-    """Join transpose ``dest[c] <- srcs[c]`` in one call."""
-    return JoinTransposition(dest, srcs).execute()
+def transpose_join_into(dest: PencilArray, srcs: Sequence[PencilArray],
+                        scale=None):
+    """Join transpose ``dest[c] <- scale * srcs[c]`` in one call."""
+    return JoinTransposition(dest, srcs, scale=scale).execute()
 
 
 # ----------------------------------------------------------------------
@@ -752,14 +778,17 @@ SIM_STAGES = ("pack", "exchange", "local", "unpack")
 def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
                  fields_per_rank: Sequence[Sequence[PencilArray]],
                  staging_out=None, stages=SIM_STAGES,
-                 staging_in=None) -> None:
+                 staging_in=None, scale=None) -> None:
     """The multi-rank simulation of a split (``aos`` on the source pencil) or
     join (``aos`` on the destination pencil) transpose: the stages and the
     n-field staging layout of :func:`run_transpose_sim_many`, with the
     descriptors of one scalar component applied to the vector-valued side
     through ``apply_copy_soa``.  ``stages`` names the stages to run and
     ``staging_in`` supplies ``send`` / ``recv`` buffers, so that one side of
-    a hop can be run by the ordinary n-field stages."""
+    a hop can be run by the ordinary n-field stages.  ``scale`` multiplies in
+    the stages the engine multiplies in, on the real view of what the stage
+    reads: a split's pack and local copy (staging holds scaled scalars), a
+    join's local copy and unpack (staging holds unscaled ones)."""
     unknown = set(stages) - set(SIM_STAGES)
     if unknown:
         raise ValueError(f"unknown stages {sorted(unknown)}")
@@ -776,6 +805,12 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
             (fs[0].pencil, a.pencil)
         plans.append(build_plan(Pi, Po, r, a.extra_dims))
     dt = aos_per_rank[0].data.dtype
+    sc = resolve_scale(dt, scale)
+
+    def scaled(x):
+        """What a multiplying stage reads: ``x (*) a``, or ``x`` itself."""
+        return x if sc is None else scale_array(x, sc.alpha)
+
     if staging_in is not None:
         send_bufs, recv_bufs = staging_in["send"], staging_in["recv"]
     else:
@@ -787,18 +822,23 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
 
     for r, p in enumerate(plans):
         aos, fs = aos_per_rank[r].data, fields_per_rank[r]
+        src_aos = scaled(aos) if split and (pack or local) else aos
         for c in range(n):
             if pack:
                 for which, d in stage_descs(p, n, c, 0):
                     assert which == 1, "a split or join plan is not aliased"
                     if split:
-                        apply_copy_soa(d, aos, send_bufs[r], n, c, True)
+                        apply_copy_soa(d, src_aos, send_bufs[r], n, c, True)
                     else:
                         apply_copy(d, fs[c].data, send_bufs[r])
             if local:
                 for which, d in stage_descs(p, n, c, 1):
                     assert which == 0, "a split or join plan is not aliased"
-                    apply_copy_soa(d, aos, fs[c].data, n, c, split)
+                    if split:
+                        apply_copy_soa(d, src_aos, fs[c].data, n, c, True)
+                    else:
+                        apply_copy_soa(d, aos, scaled(fs[c].data), n, c,
+                                       False)
 
     # exchange: ONE slice copy per peer pair, all n components in it
     if exchange:
@@ -818,12 +858,13 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
     if unpack:
         for r, p in enumerate(plans):
             aos, fs = aos_per_rank[r].data, fields_per_rank[r]
+            src_recv = recv_bufs[r] if split else scaled(recv_bufs[r])
             for c in range(n):
                 for which, d in stage_descs(p, n, c, 2):
                     if split:
                         apply_copy(d, recv_bufs[r], fs[c].data)
                     else:
-                        apply_copy_soa(d, aos, recv_bufs[r], n, c, False)
+                        apply_copy_soa(d, aos, src_recv, n, c, False)
     if staging_out is not None:
         staging_out["send"] = send_bufs
         staging_out["recv"] = recv_bufs
@@ -832,7 +873,7 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
 def run_transpose_sim_split(dests_per_rank: Sequence[Sequence[PencilArray]],
                             srcs: Sequence[PencilArray],
                             staging_out=None, stages=SIM_STAGES,
-                            staging_in=None) -> None:
+                            staging_in=None, scale=None) -> None:
     """Every rank's split transpose ``dests_per_rank[r][c] <- srcs[r][c]``
     (:class:`SplitTransposition`) with the n-field staging layout of
     :func:`run_transpose_sim_many`: the pack reads the vector-valued source
@@ -841,18 +882,24 @@ def run_transpose_sim_split(dests_per_rank: Sequence[Sequence[PencilArray]],
     ``staging_out``, if a dict, receives the ``send`` / ``recv`` buffers per
     rank, in scalars.  ``stages`` (a subset of ``SIM_STAGES``) runs only
     those stages, on the buffers of ``staging_in`` if given: the way to put
-    an ordinary n-field stage on the other side of a hop."""
-    _run_sim_soa(True, srcs, dests_per_rank, staging_out, stages, staging_in)
+    an ordinary n-field stage on the other side of a hop.  ``scale``: the
+    pack and the local copy multiply, so the buffers hold the SCALED scalars,
+    byte for byte those of :func:`run_transpose_sim_many` on the scaled
+    component copies, and the ordinary unpack delivers the scaled fields."""
+    _run_sim_soa(True, srcs, dests_per_rank, staging_out, stages, staging_in,
+                 scale)
 
 
 def run_transpose_sim_join(dests: Sequence[PencilArray],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
                            staging_out=None, stages=SIM_STAGES,
-                           staging_in=None) -> None:
+                           staging_in=None, scale=None) -> None:
     """Every rank's join transpose ``dests[r][c] <- srcs_per_rank[r][c]``
     (:class:`JoinTransposition`): the ordinary n-field pack, one slice copy
     per peer pair, and an unpack that writes the vector-valued destination
     from the ``n`` component slots of every recv block.  ``staging_out``,
-    ``stages`` and ``staging_in`` as in :func:`run_transpose_sim_split`."""
+    ``stages`` and ``staging_in`` as in :func:`run_transpose_sim_split`.
+    ``scale``: the local copy and the unpack multiply; the buffers hold
+    unscaled scalars, byte for byte those of the run without a scale."""
     _run_sim_soa(False, dests, srcs_per_rank, staging_out, stages,
-                 staging_in)
+                 staging_in, scale)

@@ -2,7 +2,11 @@
 """Compare two `-Rpass-analysis=kernel-resource-usage` logs of the engine.
 
     hipcc ... -Rpass-analysis=kernel-resource-usage pencilhip.hip 2> new.log
-    python tools/resource_report.py parent.log new.log
+    python tools/resource_report.py [--none-policy NAME] parent.log new.log
+
+``--none-policy NAME`` (repeatable) compares by demangled name with every
+``, NAME`` dropped: a kernel that gained a defaulted policy template parameter
+is then matched with its parent form under the policy's "none" instance NAME.
 
 Prints one line per kernel (demangled name, SGPRs, VGPRs, AGPRs, scratch
 bytes per lane, occupancy, spills, LDS bytes), the kernels only the second
@@ -47,9 +51,31 @@ def row(v):
     return " ".join(f"{s}={v.get(f, '?')}" for s, f in zip(SHORT, FIELDS))
 
 
+def rekey(table, dm, none):
+    """Key ``table`` by demangled name with every ``, POLICY`` of ``none``
+    dropped, so that a kernel which only gained a defaulted policy parameter
+    meets its parent form under that parameter's "none" instance."""
+    out = {}
+    for n, v in table.items():
+        k = dm[n]
+        for pol in none:
+            k = k.replace(", " + pol, "")
+        out[k] = v
+    return out
+
+
 def main():
-    old, new = parse(sys.argv[1]), parse(sys.argv[2])
+    args = sys.argv[1:]
+    none = []   # --none-policy NAME, repeatable
+    while "--none-policy" in args:
+        i = args.index("--none-policy")
+        none.append(args[i + 1])
+        del args[i:i + 2]
+    old, new = parse(args[0]), parse(args[1])
     dm = demangle(sorted(set(old) | set(new)))
+    if none:
+        old, new = rekey(old, dm, none), rekey(new, dm, none)
+        dm = {k: k for k in set(old) | set(new)}
     bad = 0
     moved = [n for n in old if n in new and old[n] != new[n]]
     gone = [n for n in old if n not in new]
