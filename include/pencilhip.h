@@ -91,9 +91,13 @@ void pa_comm_destroy(pa_comm *c);
  * Transpositions.jl:510-517).
  * flags bit 1 (PA_PLAN_GROUP_CVT): on a plan with a wire pair
  * (pa_plan_create_wire) the converting kernels of a stage run as grouped
- * launches, see there; on any other plan the bit has no effect. */
+ * launches, see there; on any other plan the bit has no effect.
+ * flags bit 2 (PA_PLAN_GROUP_SOA): on a scalar plan the split and join stage
+ * calls run as grouped launches and accept a keep plan, see "split and join
+ * transposes"; on any other plan the bit has no effect. */
 #define PA_PLAN_ALIASED 1
 #define PA_PLAN_GROUP_CVT 2
+#define PA_PLAN_GROUP_SOA 4
 pa_status pa_plan_create(const pa_pencil *pin, const pa_pencil *pout,
                          int64_t elem_size, int e, const int64_t *extra_dims,
                          int rank, int flags, pa_plan **out);
@@ -164,6 +168,10 @@ int pa_plan_wire(const pa_plan *p);
 /* 1 for a plan with a wire pair created with PA_PLAN_GROUP_CVT, else 0 (an
  * ordinary or keep plan ignores the flag). */
 int pa_plan_group_cvt(const pa_plan *p);
+/* 1 for a plan created with PA_PLAN_GROUP_SOA on which the flag has an
+ * effect: a scalar plan (ncomp == 1) of 4-, 8- or 16-byte scalars that is not
+ * aliased and has no wire pair; else 0. */
+int pa_plan_group_soa(const pa_plan *p);
 
 /* Scaled transpose: dest = alpha * T(src), the normalisation of an inverse
  * FFT folded into the pass that writes the destination anyway (the reference
@@ -455,8 +463,8 @@ int64_t pa_plan_stage_table_builds(const pa_plan *p);
  * single-group exchange of pa_transpose_execute_many, local, unpack;
  * pa_transpose_wait and pa_plan_stage_times work after them.
  * Refused with an error: a PA_PLAN_ALIASED plan (the two sides have different
- * element sizes and cannot alias), a keep plan, a wire plan, a plan with a
- * scale set, a composite plan (ncomp > 1), n < 2, S not 4, 8 or 16.
+ * element sizes and cannot alias), a keep plan (unless the plan was created
+ * with PA_PLAN_GROUP_SOA, below), a wire plan, a plan with a scale set, a composite plan (ncomp > 1), n < 2, S not 4, 8 or 16.
  *
  * A scale is given PER CALL, to the *_scaled forms below, exactly as n is: the
  * plan stays the ordinary scalar plan, because a plan on which
@@ -489,7 +497,37 @@ int64_t pa_plan_stage_table_builds(const pa_plan *p);
  * scaling form of the selected kernel.
  * Errors, raised before any pointer is touched: everything the plain calls
  * refuse, with their messages; then an unknown scalar code, a NaN or infinite
- * alpha, an (S, R) pair outside the four above. */
+ * alpha, an (S, R) pair outside the four above.
+ *
+ * PA_PLAN_GROUP_SOA (opt-in; pa_plan_group_soa(p) == 1) changes two things
+ * about the ten calls below, and nothing about any other call, table,
+ * descriptor or byte size of the plan:
+ *  - the four stages run through stage tables in the plan's cache, keyed on
+ *    (n, direction, stage, A, the field pointers) and dropped by
+ *    pa_plan_set_buffers like the others.  The PA_KERNEL_SOA_LINEAR entries of
+ *    one stage with the same V share ONE grouped launch and so do all its
+ *    PA_KERNEL_SOA_TILE entries, in first-appearance order;
+ *    PA_KERNEL_SOA_GENERIC entries stay one launch each.  The kernels run the
+ *    bodies of the ungrouped ones, so the bytes are the same.  alpha is a
+ *    kernel argument and not part of a table: a repeated call, a call with
+ *    another alpha, and a plain call after a scaled one on the same arrays
+ *    build and allocate nothing (pa_plan_stage_table_builds);
+ *  - a keep plan (pa_plan_create_keep) is accepted.  With K its keep set,
+ *        split:  F_c[i] == A[c][i]    join:  A[c][i] == F_c[i]    i in K,
+ *    bit for bit; the destination at i outside K reads +0 with PA_FILL_ZERO
+ *    and is untouched with PA_FILL_NONE.  A scaled call multiplies the kept
+ *    scalars exactly once, in the stages that multiply without a keep set;
+ *    outside K the result is +0 whatever the sign of alpha.  Staging and
+ *    messages are byte for byte those of the n-field keep plan on the
+ *    (scaled, for a split) component copies, in kept elements, and nothing
+ *    beyond them is written; either side may face an ordinary n-field keep
+ *    peer.  The zero fill is ONE grouped PA_KERNEL_FILL launch at the end of
+ *    local_split / local_join over the pa_plan_filldesc windows: of all n
+ *    destinations for a split, and of A in elements of n * S bytes for a
+ *    join.  With the full keep set everything equals the flagged ordinary
+ *    plan's and there is no fill.
+ * An aliased, wire, composite or 2-byte plan ignores the flag and a plan with
+ * a scale set stays refused, all with the messages above. */
 pa_status pa_transpose_pack_split(pa_plan *p, int n, const void *src_aos,
                                   void *stream);
 pa_status pa_transpose_local_split(pa_plan *p, int n, const void *src_aos,
@@ -524,6 +562,27 @@ pa_status pa_transpose_execute_join_scaled(pa_plan *p, int n, int scalar,
                                            double alpha,
                                            const void *const *srcs,
                                            void *dst_aos, void *stream);
+
+/* The launches a split / join stage makes (host-only), rows as in
+ * pa_plan_stage_launches: {kind, grouped, entries, workgroups}.  Valid for
+ * (PA_SOA_SPLIT, PA_STAGE_PACK), (PA_SOA_SPLIT, PA_STAGE_LOCAL),
+ * (PA_SOA_JOIN, PA_STAGE_LOCAL) and (PA_SOA_JOIN, PA_STAGE_UNPACK); a split's
+ * unpack and a join's pack are ordinary n-field stages and an error here that
+ * names pa_plan_stage_launches.  aos and fields (fields is used by the local
+ * stage only) matter for their alignment; NULL ones are taken as aligned, and
+ * so is staging not yet set.  A plan without PA_PLAN_GROUP_SOA reports one
+ * ungrouped row per non-empty descriptor, which is what its stage calls
+ * launch (a PA_KERNEL_SOA_GENERIC row of n > 8 fields is several launches of
+ * up to 8; its workgroups are those of all n).  A plan with the flag reports
+ * the grouped rows, workgroups being the sum of the entries' grids, and on a
+ * keep plan with PA_FILL_ZERO the PA_KERNEL_FILL row that ends the local
+ * stage: n * pa_plan_nfill entries for a split, pa_plan_nfill for a join.
+ * The stage calls execute exactly this list.  Errors: what the stage calls
+ * refuse about the plan and n, an unknown dir or stage. */
+pa_status pa_plan_stage_launches_soa(const pa_plan *p, int n, int dir,
+                                     int stage, const void *aos,
+                                     const void *const *fields, int max_rows,
+                                     int64_t (*rows)[4], int *nrows);
 
 /* ---- reductions (src/reductions.jl:9-38) ----------------------------- */
 /* One ncclAllReduce over a communicator (normally the FULL topology comm):

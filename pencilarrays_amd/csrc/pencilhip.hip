@@ -1283,14 +1283,18 @@ template <int N, typename M = SoaNoMul> struct SoaPtrs : M { void *p[N]; };
  * field gets one V-scalar vector; the interleave between them happens in
  * registers with compile-time indices.  The descriptor is in units of V
  * scalars.  The N AoS accesses of a wave cover one contiguous range of
- * 64*N*V scalars, every byte of it exactly once. */
-template <typename S, int DIR, int N, int V, typename M = SoaNoMul>
-__global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
-                                                    SoaPtrs<N, M> f,
-                                                    DescDev d)
+ * 64*N*V scalars, every byte of it exactly once.
+ *
+ * The body is shared by k_soa_linear and the grouped k_group_soa_linear: fp
+ * points at the N field pointers where they lie (the kernel arguments, or an
+ * entry of the grouped table), f is the multiplier policy, b the
+ * (entry-local) flat block id. */
+template <typename S, int DIR, int N, int V, typename M>
+__device__ __forceinline__ void soa_linear_body(void *__restrict__ aos_,
+                                                void *const *fp, const M &f,
+                                                const DescDev &d, int64_t b)
 {
     typedef VecT<S, V> SV;
-    const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const int64_t run = d.dims[0];
     const int64_t idx = b * blockDim.x + threadIdx.x;
     if (idx >= d.total) return;
@@ -1320,12 +1324,12 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
             SV out;
 #pragma unroll
             for (int v = 0; v < V; v++) out.v[v] = flat[v * N + c];
-            ((SV *)f.p[c])[fo] = out;
+            ((SV *)fp[c])[fo] = out;
         }
     } else {
 #pragma unroll
         for (int c = 0; c < N; c++) {
-            const SV in = ((const SV *)f.p[c])[fo];
+            const SV in = ((const SV *)fp[c])[fo];
 #pragma unroll
             for (int v = 0; v < V; v++) flat[v * N + c] = in.v[v];
         }
@@ -1339,6 +1343,15 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
             aos[k] = out;
         }
     }
+}
+
+template <typename S, int DIR, int N, int V, typename M = SoaNoMul>
+__global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
+                                                    SoaPtrs<N, M> f,
+                                                    DescDev d)
+{
+    soa_linear_body<S, DIR, N, V, M>(
+        aos_, f.p, f, d, (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 /* The permuted case: the source side is contiguous along axis 0, the
@@ -1358,14 +1371,19 @@ __global__ __launch_bounds__(256) void k_soa_linear(void *__restrict__ aos_,
  * component tile is loaded like tile_body's (lanes along axis 0: consecutive
  * LDS words).  The AoS store reads, at word index q = j*N + c of row i,
  * c*plane + j*pitch + i; with plane == 1 and pitch == N (mod 256/W) that is
- * q + i modulo the bank span: consecutive lanes, consecutive banks. */
-template <typename S, int DIR, int N, typename M = SoaNoMul>
-__global__ __launch_bounds__(256) void k_soa_tile(
-    void *__restrict__ aos_, SoaPtrs<N, M> f, DescDev d, int ta, int ti,
-    int pitch, int plane, int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+ * q + i modulo the bank span: consecutive lanes, consecutive banks.
+ *
+ * The body is shared by k_soa_tile and the grouped k_group_soa_tile: tile is
+ * the workgroup's LDS, fp and f as in soa_linear_body (the split's store
+ * picks its field by lane, so the pointers must stay where a lane can index
+ * them: a copy in registers would go to scratch), bid the (entry-local) flat
+ * block id, already checked against the block count. */
+template <typename S, int DIR, int N, typename M>
+__device__ __forceinline__ void soa_tile_body(
+    S *tile, void *__restrict__ aos_, void *const *fp, const M &f,
+    const DescDev &d, int ta, int ti, int pitch, int plane, int64_t ntile_i,
+    int64_t ntile_j, int64_t bid)
 {
-    extern __shared__ uint4 soa_lds[];
-    S *tile = (S *)soa_lds;
     constexpr int NR = 4;
     constexpr int TJ = PA_SOA_TILE_TJ;
     static_assert(N * TJ <= 64, "the components of a split store share a wave");
@@ -1373,8 +1391,6 @@ __global__ __launch_bounds__(256) void k_soa_tile(
     const int tx = threadIdx.x; /* 0..63 */
     const int ty = threadIdx.y; /* 0..NR-1 */
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (bid >= nblocks) return;
     const int64_t t_i = bid % ntile_i;
     int64_t rest = bid / ntile_i;
     const int64_t t_j = rest % ntile_j;
@@ -1412,10 +1428,10 @@ __global__ __launch_bounds__(256) void k_soa_tile(
         {
             const int c = tx / TJ, j = tx % TJ;
             if (c < N && j < nj) {
-                S *dst = (S *)f.p[0];
+                S *dst = (S *)fp[0];
 #pragma unroll
                 for (int cc = 1; cc < N; cc++)
-                    if (c == cc) dst = (S *)f.p[cc];
+                    if (c == cc) dst = (S *)fp[cc];
                 dst += do_b + j0 + i0 * di + j;
                 const S *tcol = tile + j * pitch + c;
                 for (int i = ty; i < ni; i += NR)
@@ -1428,7 +1444,7 @@ __global__ __launch_bounds__(256) void k_soa_tile(
             const int64_t fbase = so_b + i0 + j0 * sj;
 #pragma unroll
             for (int c = 0; c < N; c++) {
-                const S *src = (const S *)f.p[c] + fbase;
+                const S *src = (const S *)fp[c] + fbase;
                 for (int j = ty; j < nj; j += NR) {
                     const S *row = src + (int64_t)j * sj;
                     S *trow = tile + c * plane + j * pitch;
@@ -1450,6 +1466,59 @@ __global__ __launch_bounds__(256) void k_soa_tile(
             }
         }
     }
+}
+
+template <typename S, int DIR, int N, typename M = SoaNoMul>
+__global__ __launch_bounds__(256) void k_soa_tile(
+    void *__restrict__ aos_, SoaPtrs<N, M> f, DescDev d, int ta, int ti,
+    int pitch, int plane, int64_t ntile_i, int64_t ntile_j, int64_t nblocks)
+{
+    extern __shared__ uint4 soa_lds[];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    soa_tile_body<S, DIR, N, M>((S *)soa_lds, aos_, f.p, f, d, ta, ti, pitch,
+                                plane, ntile_i, ntile_j, bid);
+}
+
+/* Grouped forms of the two kernels above (PA_PLAN_GROUP_SOA): one launch over
+ * a table of entries of one V resp. all tile entries of a stage; S, the
+ * direction, N and the multiplier policy are the same for every entry of a
+ * stage call.  Entry lookup is that of the other grouped kernels, so the
+ * descriptor, the base pointers and the tile shape sit on scalar registers.
+ * The multiplier is a kernel argument: the tables do not depend on alpha. */
+struct GSoa {
+    DescDev d;  /* linear: in units of V scalars; tile: scalars */
+    void *aos;  /* base pointers baked in: the table is per array set */
+    void *f[PA_SOA_TILE_MAX_N]; /* fields, or the slots of a staging block */
+    int ta, ti, pitch, plane;   /* tile kernels */
+    int64_t ntile_i, ntile_j;   /* tile kernels */
+};
+
+template <typename S, int DIR, int N, int V, typename M>
+__global__ __launch_bounds__(256) void k_group_soa_linear(
+    const int64_t *__restrict__ first, const GSoa *__restrict__ ent, int nent,
+    int64_t nblocks, M m)
+{
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GSoa &g = ent[e];
+    soa_linear_body<S, DIR, N, V, M>(g.aos, g.f, m, g.d, bid - first[e]);
+}
+
+template <typename S, int DIR, int N, typename M>
+__global__ __launch_bounds__(256) void k_group_soa_tile(
+    const int64_t *__restrict__ first, const GSoa *__restrict__ ent, int nent,
+    int64_t nblocks, M m)
+{
+    extern __shared__ uint4 soa_lds[];
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= nblocks) return;
+    const int e = group_find(first, nent, bid);
+    const GSoa &g = ent[e];
+    soa_tile_body<S, DIR, N, M>((S *)soa_lds, g.aos, g.f, m, g.d, g.ta, g.ti,
+                                g.pitch, g.plane, g.ntile_i, g.ntile_j,
+                                bid - first[e]);
 }
 
 /* Any other descriptor, any n: one lane per scalar, grid-stride like
@@ -3008,6 +3077,8 @@ struct pa_plan {
     /* PA_PLAN_GROUP_CVT was given: on a wire plan the converting entries of
      * a stage share grouped launches (build_stage); no effect otherwise */
     bool group_cvt = false;
+    /* PA_PLAN_GROUP_SOA was given: see pa_plan_group_soa() */
+    bool group_soa = false;
     /* scaled transpose (pa_plan_set_scale): the PA_SCALAR_* code, or 0 for a
      * plan without a scale; an element is nscal such scalars.  The local
      * copy, the self unpack and the unpacks multiply by alpha, which is a
@@ -3409,6 +3480,7 @@ static pa_status plan_build(const pa_pencil *pin, const pa_pencil *pout,
     pl->R = R;
     pl->aliased = (flags & PA_PLAN_ALIASED) != 0;
     pl->group_cvt = (flags & PA_PLAN_GROUP_CVT) != 0;
+    pl->group_soa = (flags & PA_PLAN_GROUP_SOA) != 0;
     if (keep_lo) {
         /* the exchange of a keep plan is always a single group */
         pl->keep = true;
@@ -3852,6 +3924,14 @@ int pa_plan_wire(const pa_plan *p) { return p ? p->wire : 0; }
 int pa_plan_group_cvt(const pa_plan *p)
 {
     return p && p->wire && p->group_cvt ? 1 : 0;
+}
+
+int pa_plan_group_soa(const pa_plan *p)
+{
+    return p && p->group_soa && !p->aliased && !p->wire && p->ncomp == 1 &&
+                   (p->ssz == 4 || p->ssz == 8 || p->ssz == 16)
+               ? 1
+               : 0;
 }
 
 pa_status pa_plan_set_scale(pa_plan *p, int scalar, double alpha)
@@ -4381,6 +4461,11 @@ struct StageItem {
     CvtSel c;
     bool fill = false; /* keep plan: a zero-fill entry, fs instead of k */
     FillSel fs;
+    /* a split / join stage (build_stage_soa): the selection s runs, on the
+     * vector-valued array and the field pointers (or staging slots) */
+    SoaSel s;
+    void *aos = nullptr;
+    std::vector<void *> fields;
     const void *src;
     void *dst;
     int64_t nti = 0, njc = 0, nblocks = 0;
@@ -4461,6 +4546,36 @@ static bool sel_groupable(const KernelSel &k, int *sig_kind)
         return true;
     }
     return false;
+}
+
+/* one zero-fill entry of a window of esz-byte elements; all of a stage share
+ * ONE grouped launch */
+static pa_status stage_add_fill(StageTable *t, const FillDescH &d,
+                                int64_t esz, void *dst)
+{
+    StageItem it;
+    it.src = nullptr;
+    it.dst = dst;
+    it.fill = true;
+    if (pa_status st = select_fill(d, esz, dst, &it.fs)) return st;
+    it.nblocks = it.fs.nblocks;
+    if (it.nblocks == 0) return 0;
+    const int idx = (int)t->items.size();
+    t->items.push_back(it);
+    for (auto &l : t->launches)
+        if (l.grouped && l.kind == PA_KERNEL_FILL) {
+            l.items.push_back(idx);
+            l.nblocks += it.nblocks;
+            return 0;
+        }
+    StageLaunch l;
+    l.kind = PA_KERNEL_FILL;
+    l.word = 0;
+    l.grouped = true;
+    l.items.push_back(idx);
+    l.nblocks = it.nblocks;
+    t->launches.push_back(l);
+    return 0;
 }
 
 /* The launch list of one stage: select_kernel_comp() per entry, entries of
@@ -4561,31 +4676,8 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
         }
         return 0;
     };
-    /* one zero-fill entry; all of a stage share ONE grouped launch */
     auto add_fill = [&](const FillDescH &d, void *dst) -> pa_status {
-        StageItem it;
-        it.src = nullptr;
-        it.dst = dst;
-        it.fill = true;
-        if (pa_status st = select_fill(d, p->esz, dst, &it.fs)) return st;
-        it.nblocks = it.fs.nblocks;
-        if (it.nblocks == 0) return 0;
-        const int idx = (int)t->items.size();
-        t->items.push_back(it);
-        for (auto &l : t->launches)
-            if (l.grouped && l.kind == PA_KERNEL_FILL) {
-                l.items.push_back(idx);
-                l.nblocks += it.nblocks;
-                return 0;
-            }
-        StageLaunch l;
-        l.kind = PA_KERNEL_FILL;
-        l.word = 0;
-        l.grouped = true;
-        l.items.push_back(idx);
-        l.nblocks = it.nblocks;
-        t->launches.push_back(l);
-        return 0;
+        return stage_add_fill(t, d, p->esz, dst);
     };
 
     for (int f = 0; f < n; f++) {
@@ -4649,6 +4741,34 @@ static pa_status upload_stage(StageTable *t)
             }
             HIP_CHECK(hipMalloc(&l.d_mem, fhost.size()));
             HIP_CHECK(hipMemcpy(l.d_mem, fhost.data(), fhost.size(),
+                                hipMemcpyHostToDevice));
+            continue;
+        }
+        if (l.kind == PA_KERNEL_SOA_LINEAR || l.kind == PA_KERNEL_SOA_TILE) {
+            std::vector<char> shost(ne * sizeof(int64_t) + ne * sizeof(GSoa));
+            int64_t *sfirst = (int64_t *)shost.data();
+            char *sent = shost.data() + ne * sizeof(int64_t);
+            int64_t sacc = 0;
+            for (size_t i = 0; i < ne; i++) {
+                const StageItem &it = t->items[l.items[i]];
+                sfirst[i] = sacc;
+                sacc += it.nblocks;
+                GSoa g;
+                memset(&g, 0, sizeof g);
+                g.d = to_dev(it.s.d);
+                g.aos = it.aos;
+                for (int c = 0; c < it.s.n && c < PA_SOA_TILE_MAX_N; c++)
+                    g.f[c] = it.fields[c];
+                g.ta = it.s.ta;
+                g.ti = it.s.ti;
+                g.pitch = it.s.pitch;
+                g.plane = it.s.plane;
+                g.ntile_i = it.nti;
+                g.ntile_j = it.njc;
+                memcpy(sent + i * sizeof(GSoa), &g, sizeof g);
+            }
+            HIP_CHECK(hipMalloc(&l.d_mem, shost.size()));
+            HIP_CHECK(hipMemcpy(l.d_mem, shost.data(), shost.size(),
                                 hipMemcpyHostToDevice));
             continue;
         }
@@ -4914,6 +5034,25 @@ static pa_status exchange_many(pa_plan *p, int n, hipStream_t stream)
     return 0;
 }
 
+/* the plan's LRU cache of stage tables: the table of `key`, or null; and room
+ * for one more, by dropping the least recently used at capacity */
+static StageTable *table_find(pa_plan *p, const std::vector<uintptr_t> &key)
+{
+    for (auto *c : p->tables)
+        if (c->key == key) return c;
+    return nullptr;
+}
+
+static void table_make_room(pa_plan *p)
+{
+    if ((int)p->tables.size() < PA_STAGE_TABLES_MAX) return;
+    size_t old = 0;
+    for (size_t i = 1; i < p->tables.size(); i++)
+        if (p->tables[i]->stamp < p->tables[old]->stamp) old = i;
+    free_table(p->tables[old]);
+    p->tables.erase(p->tables.begin() + old);
+}
+
 static pa_status run_stage(pa_plan *p, int n, int stage,
                            const void *const *srcs, void *const *dsts,
                            hipStream_t stream)
@@ -4921,17 +5060,9 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
     if (pa_status st = many_check(p, n, stage, srcs, dsts)) return st;
     std::vector<uintptr_t> key;
     stage_key(p, n, stage, srcs, dsts, &key);
-    StageTable *t = nullptr;
-    for (auto *c : p->tables)
-        if (c->key == key) { t = c; break; }
+    StageTable *t = table_find(p, key);
     if (!t) {
-        if ((int)p->tables.size() >= PA_STAGE_TABLES_MAX) {
-            size_t old = 0;
-            for (size_t i = 1; i < p->tables.size(); i++)
-                if (p->tables[i]->stamp < p->tables[old]->stamp) old = i;
-            free_table(p->tables[old]);
-            p->tables.erase(p->tables.begin() + old);
-        }
+        table_make_room(p);
         t = new StageTable;
         t->key = key;
         pa_status st = build_stage(p, n, stage, srcs, dsts, p->send_buf,
@@ -5200,8 +5331,9 @@ pa_status pa_transpose_execute_many(pa_plan *p, int n,
  * kernels: a split multiplies in pack and local, so its staging holds scaled
  * scalars; a join multiplies in local and unpack, so its staging does not. */
 
-static pa_status soa_check(const pa_plan *p, int n, const void *aos,
-                           const void *const *fields, bool need_fields)
+/* what a split or join call, and pa_plan_stage_launches_soa, refuse about
+ * the plan and n */
+static pa_status soa_check_plan(const pa_plan *p, int n)
 {
     if (!p) return fail("null plan");
     if (n < 2) return fail("n must be >= 2 (got %d)", n);
@@ -5209,14 +5341,21 @@ static pa_status soa_check(const pa_plan *p, int n, const void *aos,
         return fail("a split or join cannot run on a PA_PLAN_ALIASED plan: "
                     "the two sides have different element sizes and cannot "
                     "alias");
-    if (p->keep) return fail("a split or join cannot run on a keep plan");
+    if (p->keep && !pa_plan_group_soa(p))
+        return fail("a split or join cannot run on a keep plan");
     if (p->wire) return fail("a split or join cannot run on a wire plan");
     if (p->scale)
         return fail("a split or join cannot run on a plan with a scale set");
     if (p->ncomp > 1)
         return fail("a split or join needs a scalar plan: this one has "
                     "ncomp = %lld", (long long)p->ncomp);
-    if (pa_status st = check_soa(p->ssz, n, PA_SOA_SPLIT)) return st;
+    return check_soa(p->ssz, n, PA_SOA_SPLIT);
+}
+
+static pa_status soa_check(const pa_plan *p, int n, const void *aos,
+                           const void *const *fields, bool need_fields)
+{
+    if (pa_status st = soa_check_plan(p, n)) return st;
     if (!aos) return fail("null vector-valued array pointer");
     if (need_fields) {
         if (!fields) return fail("null field pointers");
@@ -5269,11 +5408,254 @@ static pa_status soa_scale(const pa_plan *p, int scalar, double alpha,
     return 0;
 }
 
+/* ---- stage tables of the split / join stages (PA_PLAN_GROUP_SOA) -------
+ *
+ * The launch list of (dir, stage): select_kernel_soa() per sub-block in the
+ * order the ungrouped stage loops walk them.  With `grouped` the SOA_LINEAR
+ * entries of one V share a launch and so do all SOA_TILE entries (their tile
+ * shape depends on n * S only), in first-appearance order; SOA_GENERIC
+ * entries stay one row each.  The local stage of a keep plan ends with ONE
+ * grouped PA_KERNEL_FILL row: the plan's fill windows on every field of a
+ * split, and on the vector-valued array, in elements of n * S bytes, of a
+ * join.  Host-only; staging may be any aligned stand-in. */
+static pa_status build_stage_soa(const pa_plan *p, int n, int dir, int stage,
+                                 void *aos, void *const *fields,
+                                 void *send_buf, void *recv_buf, bool grouped,
+                                 StageTable *t)
+{
+    auto add_desc = [&](const CopyDescH &d, void *const *fp) -> pa_status {
+        StageItem it;
+        it.src = nullptr;
+        it.dst = nullptr;
+        it.aos = aos;
+        it.fields.assign(fp, fp + n);
+        if (pa_status st = select_kernel_soa(d, p->ssz, n, dir, aos, fp, &it.s))
+            return st;
+        const SoaSel &k = it.s;
+        if (k.kind == PA_KERNEL_NONE) return 0; /* empty: no blocks */
+        if (k.kind == PA_KERNEL_SOA_LINEAR)
+            it.nblocks = grid_exact(k.d.total, 256);
+        else if (k.kind == PA_KERNEL_SOA_GENERIC)
+            it.nblocks = (int64_t)grid_for(k.d.total, 256) * n;
+        else {
+            int64_t nbatch = 1;
+            for (int a = 1; a < k.d.nd; a++)
+                if (a != k.ta) nbatch *= k.d.dims[a];
+            it.nti = (k.d.dims[0] + k.ti - 1) / k.ti;
+            it.njc = (k.d.dims[k.ta] + k.tj - 1) / k.tj;
+            it.nblocks = it.nti * it.njc * nbatch;
+        }
+        const bool grp = grouped && k.kind != PA_KERNEL_SOA_GENERIC;
+        const int vec = k.kind == PA_KERNEL_SOA_LINEAR ? k.V : 0;
+        const int idx = (int)t->items.size();
+        t->items.push_back(it);
+        if (grp)
+            for (auto &l : t->launches)
+                if (l.grouped && l.kind == k.kind && l.vec == vec) {
+                    l.items.push_back(idx);
+                    l.nblocks += it.nblocks;
+                    return 0;
+                }
+        StageLaunch l;
+        l.kind = k.kind;
+        l.vec = vec;
+        l.grouped = grp;
+        l.items.push_back(idx);
+        l.nblocks = it.nblocks;
+        t->launches.push_back(l);
+        return 0;
+    };
+    /* one staged block with the vector-valued array on its other side:
+     * component c's slot starts c * (block count) scalars into the block */
+    auto add_staged = [&](const SubC &sb, void *staging) -> pa_status {
+        CopyDescH d = sb.d;
+        const int64_t sh = many_shift(n, 0, sb.off, sb.n);
+        if (dir == PA_SOA_SPLIT)
+            d.doff += sh;
+        else
+            d.soff += sh;
+        std::vector<void *> slots(n);
+        for (int c = 0; c < n; c++)
+            slots[c] = (char *)staging + (int64_t)c * sb.n * p->ssz;
+        return add_desc(d, slots.data());
+    };
+
+    if (stage == STAGE_LOCAL) {
+        for (auto &sb : p->local)
+            if (pa_status st = add_desc(sb.d, fields)) return st;
+        for (int c = 0; c < (dir == PA_SOA_SPLIT ? n : 1); c++)
+            for (auto &fd : p->fills)
+                if (pa_status st =
+                        dir == PA_SOA_SPLIT
+                            ? stage_add_fill(t, fd, p->ssz, fields[c])
+                            : stage_add_fill(t, fd, (int64_t)n * p->ssz, aos))
+                    return st;
+        return 0;
+    }
+    for (auto &b : p->peers)
+        for (auto &sb : dir == PA_SOA_SPLIT ? b.pack : b.unpack)
+            if (pa_status st = add_staged(
+                    sb, dir == PA_SOA_SPLIT ? send_buf : recv_buf))
+                return st;
+    return 0;
+}
+
+/* the grouped launch of one S, multiplier policy, direction and N: V resp.
+ * the tile picks the instance, as in launch_soa_n() */
+template <typename S, typename M, int DIR, int N>
+static pa_status launch_group_soa_n(const StageLaunch &l, const SoaSel &k,
+                                    const M &m, const int64_t *first,
+                                    const GSoa *ent, int ne,
+                                    hipStream_t stream)
+{
+    dim3 grid;
+    if (pa_status gst = grid2d(l.nblocks, 256, &grid)) return gst;
+    if (l.kind == PA_KERNEL_SOA_LINEAR) {
+        constexpr int VMAX = 16 / (int)sizeof(S);
+#define GROUP_SOA_LIN(VV)                                                    \
+    hipLaunchKernelGGL((k_group_soa_linear<S, DIR, N, VV, M>), grid,         \
+                       dim3(256), 0, stream, first, ent, ne, l.nblocks, m)
+        if (l.vec < 1 || l.vec > VMAX) return fail("bad vector width %d", l.vec);
+        if constexpr (VMAX >= 4) {
+            if (l.vec == 4) { GROUP_SOA_LIN(4); return 0; }
+        }
+        if constexpr (VMAX >= 2) {
+            if (l.vec == 2) { GROUP_SOA_LIN(2); return 0; }
+        }
+        if (l.vec != 1) return fail("bad vector width %d", l.vec);
+        GROUP_SOA_LIN(1);
+#undef GROUP_SOA_LIN
+        return 0;
+    }
+    /* PA_KERNEL_SOA_TILE: one tile shape for the stage, that of entry 0 */
+    const int64_t row = DIR == PA_SOA_SPLIT ? (int64_t)k.ti * N : k.ti;
+    if (k.ta < 1 || k.ti < 1 || k.tj != PA_SOA_TILE_TJ || k.pitch < row ||
+        (DIR == PA_SOA_JOIN && k.plane < k.tj * k.pitch))
+        return fail("bad split/join tile selection");
+    const size_t lds = sizeof(S) * (DIR == PA_SOA_SPLIT
+                                        ? (size_t)k.tj * k.pitch
+                                        : (size_t)N * k.plane);
+    if (lds > (64u << 10))
+        return fail("split/join tile needs %zu B of LDS", lds);
+    hipLaunchKernelGGL((k_group_soa_tile<S, DIR, N, M>), grid, dim3(64, 4),
+                       lds, stream, first, ent, ne, l.nblocks, m);
+    return 0;
+}
+
+template <typename S, typename M, int DIR>
+static pa_status launch_group_soa_t(const StageLaunch &l, const SoaSel &k,
+                                    const M &m, const int64_t *first,
+                                    const GSoa *ent, int ne,
+                                    hipStream_t stream)
+{
+    switch (k.n) {
+    case 2:
+        return launch_group_soa_n<S, M, DIR, 2>(l, k, m, first, ent, ne, stream);
+    case 3:
+        return launch_group_soa_n<S, M, DIR, 3>(l, k, m, first, ent, ne, stream);
+    case 4:
+        return launch_group_soa_n<S, M, DIR, 4>(l, k, m, first, ent, ne, stream);
+    default: return fail("bad grouped split/join launch: n = %d", k.n);
+    }
+}
+
+/* k is the selection of the launch's first entry: S, n, the direction and
+ * (tile) the shape are the same for all of them; scalar and alpha as in
+ * launch_soa_sel() */
+static pa_status launch_group_soa(const StageLaunch &l, const SoaSel &k,
+                                  int scalar, double alpha,
+                                  hipStream_t stream)
+{
+    const int ne = (int)l.items.size();
+    const int64_t *first = (const int64_t *)l.d_mem;
+    const GSoa *ent =
+        (const GSoa *)((const char *)l.d_mem + ne * sizeof(int64_t));
+    if (scalar)
+        if (pa_status st = check_soa_scale(k.ssz, scalar, alpha)) return st;
+    pa_status st;
+    const SoaNoMul none;
+    const SoaMul<float> mf{(float)alpha};
+    const SoaMul<double> md{alpha};
+#define GROUP_SOA_DIR(S, M, m)                                               \
+    (k.dir == PA_SOA_SPLIT                                                   \
+         ? launch_group_soa_t<S, M, PA_SOA_SPLIT>(l, k, m, first, ent, ne,   \
+                                                  stream)                    \
+         : launch_group_soa_t<S, M, PA_SOA_JOIN>(l, k, m, first, ent, ne,    \
+                                                 stream))
+    if (k.ssz == 4)
+        st = scalar ? GROUP_SOA_DIR(uint32_t, SoaMul<float>, mf)
+                    : GROUP_SOA_DIR(uint32_t, SoaNoMul, none);
+    else if (k.ssz == 8)
+        st = scalar == PA_SCALAR_F32
+                 ? GROUP_SOA_DIR(uint64_t, SoaMul<float>, mf)
+             : scalar == PA_SCALAR_F64
+                 ? GROUP_SOA_DIR(uint64_t, SoaMul<double>, md)
+                 : GROUP_SOA_DIR(uint64_t, SoaNoMul, none);
+    else if (k.ssz == 16)
+        st = scalar ? GROUP_SOA_DIR(uint4, SoaMul<double>, md)
+                    : GROUP_SOA_DIR(uint4, SoaNoMul, none);
+    else
+        return fail("bad scalar size %d", k.ssz);
+#undef GROUP_SOA_DIR
+    if (st) return st;
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+/* One split / join stage of a PA_PLAN_GROUP_SOA plan through its cached
+ * table.  The key is (n, direction, stage, the vector-valued array, the field
+ * pointers); neither the scale nor alpha is part of it, so a scaled call, a
+ * plain one and one with another alpha share a table. */
+static pa_status run_stage_soa(pa_plan *p, int n, int dir, int stage,
+                               void *aos, void *const *fields, int scale,
+                               double alpha, hipStream_t stream)
+{
+    std::vector<uintptr_t> key;
+    key.push_back((uintptr_t)n);
+    /* past every stage code of stage_key() */
+    key.push_back((uintptr_t)(16 + 4 * dir + stage));
+    key.push_back((uintptr_t)p->send_buf);
+    key.push_back((uintptr_t)p->recv_buf);
+    key.push_back((uintptr_t)aos);
+    for (int c = 0; c < n; c++)
+        key.push_back(stage == STAGE_LOCAL ? (uintptr_t)fields[c] : 0);
+    StageTable *t = table_find(p, key);
+    if (!t) {
+        table_make_room(p);
+        t = new StageTable;
+        t->key = key;
+        pa_status st = build_stage_soa(p, n, dir, stage, aos, fields,
+                                       p->send_buf, p->recv_buf, true, t);
+        if (!st) st = upload_stage(t);
+        if (st) { free_table(t); return st; }
+        p->tables.push_back(t);
+        p->table_builds++;
+    }
+    t->stamp = ++p->table_clock;
+    for (auto &l : t->launches) {
+        const StageItem &it = t->items[l.items[0]];
+        pa_status st;
+        if (l.kind == PA_KERNEL_FILL)
+            st = launch_group(p, l, stream);
+        else if (l.grouped)
+            st = launch_group_soa(l, it.s, scale, alpha, stream);
+        else
+            st = launch_soa_sel(it.s, it.aos, it.fields.data(), scale, alpha,
+                                stream);
+        if (st) return st;
+    }
+    return 0;
+}
+
 /* The four stages behind the plain and the scaled calls, arguments already
- * checked; scale as soa_scale() returns it (0: none). */
+ * checked; scale as soa_scale() returns it (0: none).  A PA_PLAN_GROUP_SOA
+ * plan runs them through its stage tables. */
 static pa_status soa_pack_split(pa_plan *p, int n, const void *src_aos,
                                 int scale, double alpha, hipStream_t stream)
 {
+    if (pa_plan_group_soa(p))
+        return run_stage_soa(p, n, PA_SOA_SPLIT, STAGE_PACK, (void *)src_aos,
+                             nullptr, scale, alpha, stream);
     for (auto &b : p->peers)
         for (auto &sb : b.pack)
             if (pa_status st =
@@ -5287,6 +5669,9 @@ static pa_status soa_local(pa_plan *p, int n, int dir, void *aos,
                            void *const *fields, int scale, double alpha,
                            hipStream_t stream)
 {
+    if (pa_plan_group_soa(p))
+        return run_stage_soa(p, n, dir, STAGE_LOCAL, aos, fields, scale,
+                             alpha, stream);
     for (auto &sb : p->local)
         if (pa_status st = launch_desc_soa(sb.d, p->ssz, n, dir, aos, fields,
                                            stream, scale, alpha))
@@ -5297,6 +5682,9 @@ static pa_status soa_local(pa_plan *p, int n, int dir, void *aos,
 static pa_status soa_unpack_join(pa_plan *p, int n, void *dst_aos, int scale,
                                  double alpha, hipStream_t stream)
 {
+    if (pa_plan_group_soa(p))
+        return run_stage_soa(p, n, PA_SOA_JOIN, STAGE_UNPACK, dst_aos,
+                             nullptr, scale, alpha, stream);
     for (auto &b : p->peers)
         for (auto &sb : b.unpack)
             if (pa_status st = soa_staged(p, n, PA_SOA_JOIN, sb, dst_aos,
@@ -5361,6 +5749,46 @@ pa_status pa_copy_kernel_kind_soa(int nd, const int64_t *dims,
     out[2] = k.ti;
     out[3] = k.tj;
     out[4] = 1; /* the split/join tile sweeps one tile per workgroup */
+    return 0;
+}
+
+pa_status pa_plan_stage_launches_soa(const pa_plan *p, int n, int dir,
+                                     int stage, const void *aos,
+                                     const void *const *fields, int max_rows,
+                                     int64_t (*rows)[4], int *nrows)
+{
+    if (!nrows || (max_rows > 0 && !rows)) return fail("null argument");
+    if (pa_status st = soa_check_plan(p, n)) return st;
+    if (dir != PA_SOA_SPLIT && dir != PA_SOA_JOIN)
+        return fail("unknown direction %d: PA_SOA_SPLIT or PA_SOA_JOIN", dir);
+    if (stage < STAGE_PACK || stage > STAGE_UNPACK)
+        return fail("bad stage %d", stage);
+    if (stage == (dir == PA_SOA_SPLIT ? STAGE_UNPACK : STAGE_PACK))
+        return fail("the %s of a %s is the ordinary n-field stage: ask "
+                    "pa_plan_stage_launches",
+                    dir == PA_SOA_SPLIT ? "unpack" : "pack",
+                    dir == PA_SOA_SPLIT ? "split" : "join");
+    /* staging as set, else assumed 256-byte aligned, like absent pointers;
+     * never dereferenced */
+    void *send = p->send_buf ? p->send_buf : (void *)256;
+    void *recv = p->recv_buf ? p->recv_buf : (void *)256;
+    std::vector<void *> f(n, (void *)256);
+    for (int c = 0; fields && c < n; c++)
+        if (fields[c]) f[c] = (void *)fields[c];
+    StageTable t;
+    if (pa_status st = build_stage_soa(p, n, dir, stage,
+                                       aos ? (void *)aos : (void *)256,
+                                       f.data(), send, recv,
+                                       pa_plan_group_soa(p) != 0, &t))
+        return st;
+    *nrows = (int)t.launches.size();
+    for (int i = 0; i < *nrows && i < max_rows; i++) {
+        const StageLaunch &l = t.launches[i];
+        rows[i][0] = l.kind;
+        rows[i][1] = l.grouped ? 1 : 0;
+        rows[i][2] = (int64_t)l.items.size();
+        rows[i][3] = l.nblocks;
+    }
     return 0;
 }
 

@@ -124,7 +124,7 @@ class KernelKind(NamedTuple):
 
 STAGE_PACK, STAGE_LOCAL, STAGE_UNPACK = 0, 1, 2
 # flags of the plan creators
-PLAN_ALIASED, PLAN_GROUP_CVT = 1, 2
+PLAN_ALIASED, PLAN_GROUP_CVT, PLAN_GROUP_SOA = 1, 2, 4
 
 
 class StageLaunch(NamedTuple):
@@ -381,7 +381,8 @@ class NativePlan:
     def __init__(self, Pi, Po, rank: int, elem_size: int,
                  extra_dims: Tuple[int, ...] = (), aliased: bool = False,
                  ncomp: int = 1, wire: Optional[int] = None,
-                 keep=None, fill: int = FILL_ZERO, group_cvt: bool = False):
+                 keep=None, fill: int = FILL_ZERO, group_cvt: bool = False,
+                 group_soa: bool = False):
         """``ncomp > 1``: elements of ``ncomp`` scalars of ``elem_size``
         bytes, components fastest (pa_plan_create_comp).  ``wire``: a wire
         pair code (WIRE_F64_F32, ...) for a reduced-precision wire plan
@@ -389,7 +390,10 @@ class NativePlan:
         size.  ``keep``: ``(a, b)`` per logical dim for a truncated transpose
         (pa_plan_create_keep) with ``fill`` FILL_ZERO or FILL_NONE.
         ``group_cvt``: set PA_PLAN_GROUP_CVT, which on a wire plan groups the
-        converting kernels of a stage and has no effect on any other plan."""
+        converting kernels of a stage and has no effect on any other plan.
+        ``group_soa``: set PA_PLAN_GROUP_SOA, which on a scalar plan makes the
+        split and join stages grouped launches and lets them run on a keep
+        plan, and has no effect on any other plan."""
         if keep is not None and wire is not None:
             raise ValueError(
                 "a keep set together with a wire pair is not supported")
@@ -424,7 +428,8 @@ class NativePlan:
         self.wire = wire
         self.keep = None
         flags = (PLAN_ALIASED if aliased else 0) | \
-            (PLAN_GROUP_CVT if group_cvt else 0)
+            (PLAN_GROUP_CVT if group_cvt else 0) | \
+            (PLAN_GROUP_SOA if group_soa else 0)
         if keep is not None:
             keep = list(keep)
             nk = len(keep)
@@ -472,6 +477,11 @@ class NativePlan:
         """True on a wire plan created with ``group_cvt=True``
         (pa_plan_group_cvt)."""
         return bool(self.lib.pa_plan_group_cvt(self._plan))
+
+    def group_soa(self) -> bool:
+        """True on a plan created with ``group_soa=True`` on which the flag
+        has an effect (pa_plan_group_soa)."""
+        return bool(self.lib.pa_plan_group_soa(self._plan))
 
     def set_scale(self, scalar: int, alpha: float):
         """Make this a scaled plan, ``dest = alpha * T(src)`` per real scalar
@@ -771,6 +781,27 @@ class NativePlan:
                 self._plan, n, stage, self._ptrs(src_ptrs, n),
                 self._ptrs(dst_ptrs, n), cap, rows, ctypes.byref(nrows)),
                 "pa_plan_stage_launches")
+            if nrows.value <= cap:
+                break
+            cap = nrows.value
+        return [StageLaunch(int(r[0]), bool(r[1]), int(r[2]), int(r[3]))
+                for r in rows[:nrows.value]]
+
+    def stage_launches_soa(self, n: int, direction: int, stage: int,
+                           aos_ptr: int = 0, field_ptrs=None):
+        """The launches a split / join stage makes for ``n`` components
+        (pa_plan_stage_launches_soa): ``direction`` SOA_SPLIT or SOA_JOIN,
+        ``stage`` the pack or local stage of a split, the local or unpack
+        stage of a join.  A list of :class:`StageLaunch`.  Host-only;
+        pointers (optional) are used for alignment only."""
+        cap = 64
+        while True:
+            rows = ((I64 * 4) * cap)()
+            nrows = ctypes.c_int()
+            _check(self.lib, self.lib.pa_plan_stage_launches_soa(
+                self._plan, n, direction, stage, VP(aos_ptr or None),
+                self._ptrs(field_ptrs, n), cap, rows, ctypes.byref(nrows)),
+                "pa_plan_stage_launches_soa")
             if nrows.value <= cap:
                 break
             cap = nrows.value
@@ -1110,7 +1141,9 @@ class NativeSoaTransposition(NativeMultiTransposition):
     def __init__(self, t):
         plan, f0 = t.plan, t.fields[0]
         self._setup(NativePlan(plan.Pi, plan.Po, plan.rank,
-                               f0.data.element_size(), plan.extra_dims),
+                               f0.data.element_size(), plan.extra_dims,
+                               keep=plan.keep, fill=plan.fill,
+                               group_soa=getattr(t, "grouped", False)),
                     plan, t.n, f0.data.device)
         self.split = t.split
         self.scale = getattr(t, "scale", None)  # scale.Scale or None

@@ -539,16 +539,25 @@ class _SoaTransposition:
     split: bool
 
     def __init__(self, aos: PencilArray, fields: Sequence[PencilArray],
-                 scale=None):
+                 scale=None, keep=None, fill="zero", grouped=None):
         self.aos, self.fields = aos, list(fields)
         self.n = _check_soa(aos, self.fields)
         # scale.Scale or None; None and 1.0 give the unscaled object
         self.scale = resolve_scale(aos.data.dtype, scale)
+        self.keep, self.fill = keep, fill
+        # grouped launches (PA_PLAN_GROUP_SOA) are what lets the native
+        # stages run on a keep plan
+        self.grouped = keep is not None if grouped is None else bool(grouped)
+        if keep is not None and not self.grouped:
+            raise ValueError(
+                "keep needs grouped launches: a truncated split or join "
+                "transpose cannot run with grouped=False")
         f0 = self.fields[0]
         Pi, Po = (aos.pencil, f0.pencil) if self.split else \
             (f0.pencil, aos.pencil)
         self.plan: TransposePlan = build_plan(Pi, Po, aos.rank,
-                                              aos.extra_dims)
+                                              aos.extra_dims, keep=keep,
+                                              fill=fill)
         self._native = None
 
     def _component(self, c: int) -> PencilArray:
@@ -564,13 +573,16 @@ class _SoaTransposition:
         # single-field Transposition per component, which multiplies on the
         # real view (scale.py)
         alpha = self.scale and self.scale.alpha
+        kw = dict(scale=alpha, keep=self.keep, fill=self.fill)
         if self.split:
             for c, f in enumerate(self.fields):
-                Transposition(f, self._component(c), scale=alpha).execute()
+                Transposition(f, self._component(c), **kw).execute()
         else:
             for c, f in enumerate(self.fields):
+                # the copy holds what the destination holds, which is what
+                # fill=None leaves outside the keep set
                 tmp = self._component(c)
-                Transposition(tmp, f, scale=alpha).execute()
+                Transposition(tmp, f, **kw).execute()
                 self.aos.data.reshape(-1, self.n)[:, c] = tmp.data
 
     def execute(self, sync: bool = True):
@@ -617,13 +629,26 @@ class SplitTransposition(_SoaTransposition):
     (pa_transpose_execute_split_scaled).  Staging and messages therefore carry
     the SCALED scalars, those of ``MultiTransposition`` on the scaled component
     copies: the unpack is the ordinary one and cannot multiply.  Integer
-    arrays take no scale (``ValueError``)."""
+    arrays take no scale (``ValueError``).
+
+    ``keep`` / ``fill`` (as in :class:`Transposition`) make it a truncated
+    split: only the elements of the keep set are moved,
+    ``dests[c][i] == src[c][i]`` (times ``scale``) for ``i`` in the keep set,
+    and outside it every destination reads ``+0`` (``fill="zero"``) or is
+    left untouched (``fill=None``).  Staging and messages are those of
+    ``MultiTransposition(keep=...)`` on the component copies.
+
+    ``grouped``: run each stage as one grouped launch per kernel signature
+    instead of one launch per block (PA_PLAN_GROUP_SOA); the result is the
+    same bit for bit.  ``None`` means "exactly when ``keep`` is given": a
+    keep plan needs the grouped stages, so ``keep`` with ``grouped=False``
+    is a ``ValueError``."""
 
     split = True
 
     def __init__(self, dests: Sequence[PencilArray], src: PencilArray,
-                 scale=None):
-        super().__init__(src, dests, scale)
+                 scale=None, keep=None, fill="zero", grouped=None):
+        super().__init__(src, dests, scale, keep, fill, grouped)
         self.src, self.dests = src, self.fields
 
 
@@ -638,26 +663,33 @@ class JoinTransposition(_SoaTransposition):
     (pa_transpose_execute_join_scaled): the multiply sits in the local copy
     and the unpack, the destination side as in a scaled
     :class:`Transposition`, and staging and messages carry unscaled bytes,
-    identical to the unscaled join's."""
+    identical to the unscaled join's.
+
+    ``keep`` / ``fill`` / ``grouped``: as in :class:`SplitTransposition`;
+    the zero fill covers the whole elements of ``dest`` outside the keep
+    set.  With ``keep``, ``fill="zero"`` and ``scale=1/N`` this is the
+    inverse hop of a dealiased pseudo-spectral step."""
 
     split = False
 
     def __init__(self, dest: PencilArray, srcs: Sequence[PencilArray],
-                 scale=None):
-        super().__init__(dest, srcs, scale)
+                 scale=None, keep=None, fill="zero", grouped=None):
+        super().__init__(dest, srcs, scale, keep, fill, grouped)
         self.dest, self.srcs = dest, self.fields
 
 
 def transpose_split_into(dests: Sequence[PencilArray], src: PencilArray,
-                         scale=None):
+                         scale=None, keep=None, fill="zero", grouped=None):
     """Split transpose ``dests[c] <- scale * src[c]`` in one call."""
-    return SplitTransposition(dests, src, scale=scale).execute()
+    return SplitTransposition(dests, src, scale=scale, keep=keep, fill=fill,
+                              grouped=grouped).execute()
 
 
 def transpose_join_into(dest: PencilArray, srcs: Sequence[PencilArray],
-                        scale=None):
+                        scale=None, keep=None, fill="zero", grouped=None):
     """Join transpose ``dest[c] <- scale * srcs[c]`` in one call."""
-    return JoinTransposition(dest, srcs, scale=scale).execute()
+    return JoinTransposition(dest, srcs, scale=scale, keep=keep, fill=fill,
+                             grouped=grouped).execute()
 
 
 # ----------------------------------------------------------------------
@@ -778,7 +810,8 @@ SIM_STAGES = ("pack", "exchange", "local", "unpack")
 def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
                  fields_per_rank: Sequence[Sequence[PencilArray]],
                  staging_out=None, stages=SIM_STAGES,
-                 staging_in=None, scale=None) -> None:
+                 staging_in=None, scale=None, keep=None,
+                 fill="zero") -> None:
     """The multi-rank simulation of a split (``aos`` on the source pencil) or
     join (``aos`` on the destination pencil) transpose: the stages and the
     n-field staging layout of :func:`run_transpose_sim_many`, with the
@@ -788,7 +821,10 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
     a hop can be run by the ordinary n-field stages.  ``scale`` multiplies in
     the stages the engine multiplies in, on the real view of what the stage
     reads: a split's pack and local copy (staging holds scaled scalars), a
-    join's local copy and unpack (staging holds unscaled ones)."""
+    join's local copy and unpack (staging holds unscaled ones).  ``keep`` /
+    ``fill``: the plans are keep plans, so staging holds the kept elements
+    only, and the local stage zero-fills the plan's fill windows: on every
+    field of a split, on the whole elements of ``aos`` of a join."""
     unknown = set(stages) - set(SIM_STAGES)
     if unknown:
         raise ValueError(f"unknown stages {sorted(unknown)}")
@@ -803,7 +839,8 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
             raise ValueError("every rank needs the same number of fields")
         Pi, Po = (a.pencil, fs[0].pencil) if split else \
             (fs[0].pencil, a.pencil)
-        plans.append(build_plan(Pi, Po, r, a.extra_dims))
+        plans.append(build_plan(Pi, Po, r, a.extra_dims, keep=keep,
+                                fill=fill))
     dt = aos_per_rank[0].data.dtype
     sc = resolve_scale(dt, scale)
 
@@ -839,6 +876,13 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
                     else:
                         apply_copy_soa(d, aos, scaled(fs[c].data), n, c,
                                        False)
+        if local:
+            for fd in p.fills:  # element units: n scalars on the aos side
+                if split:
+                    for f in fs:
+                        apply_fill(fd, f.element_view())
+                else:
+                    apply_fill(fd, aos_per_rank[r].element_view())
 
     # exchange: ONE slice copy per peer pair, all n components in it
     if exchange:
@@ -873,7 +917,8 @@ def _run_sim_soa(split: bool, aos_per_rank: Sequence[PencilArray],
 def run_transpose_sim_split(dests_per_rank: Sequence[Sequence[PencilArray]],
                             srcs: Sequence[PencilArray],
                             staging_out=None, stages=SIM_STAGES,
-                            staging_in=None, scale=None) -> None:
+                            staging_in=None, scale=None, keep=None,
+                            fill="zero") -> None:
     """Every rank's split transpose ``dests_per_rank[r][c] <- srcs[r][c]``
     (:class:`SplitTransposition`) with the n-field staging layout of
     :func:`run_transpose_sim_many`: the pack reads the vector-valued source
@@ -885,21 +930,26 @@ def run_transpose_sim_split(dests_per_rank: Sequence[Sequence[PencilArray]],
     an ordinary n-field stage on the other side of a hop.  ``scale``: the
     pack and the local copy multiply, so the buffers hold the SCALED scalars,
     byte for byte those of :func:`run_transpose_sim_many` on the scaled
-    component copies, and the ordinary unpack delivers the scaled fields."""
+    component copies, and the ordinary unpack delivers the scaled fields.
+    ``keep`` / ``fill``: a truncated split, staging byte for byte that of
+    :func:`run_transpose_sim_many` with the same ``keep``; the mirror has no
+    launches, so there is no ``grouped`` here."""
     _run_sim_soa(True, srcs, dests_per_rank, staging_out, stages, staging_in,
-                 scale)
+                 scale, keep, fill)
 
 
 def run_transpose_sim_join(dests: Sequence[PencilArray],
                            srcs_per_rank: Sequence[Sequence[PencilArray]],
                            staging_out=None, stages=SIM_STAGES,
-                           staging_in=None, scale=None) -> None:
+                           staging_in=None, scale=None, keep=None,
+                           fill="zero") -> None:
     """Every rank's join transpose ``dests[r][c] <- srcs_per_rank[r][c]``
     (:class:`JoinTransposition`): the ordinary n-field pack, one slice copy
     per peer pair, and an unpack that writes the vector-valued destination
     from the ``n`` component slots of every recv block.  ``staging_out``,
     ``stages`` and ``staging_in`` as in :func:`run_transpose_sim_split`.
     ``scale``: the local copy and the unpack multiply; the buffers hold
-    unscaled scalars, byte for byte those of the run without a scale."""
+    unscaled scalars, byte for byte those of the run without a scale.
+    ``keep`` / ``fill``: as in :func:`run_transpose_sim_split`."""
     _run_sim_soa(False, dests, srcs_per_rank, staging_out, stages,
-                 staging_in, scale)
+                 staging_in, scale, keep, fill)
