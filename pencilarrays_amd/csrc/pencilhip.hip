@@ -1944,276 +1944,219 @@ static pa_status select_kernel_comp(const CopyDescH &dn, int64_t ssz,
     }
 }
 
-template <typename WordT>
-static pa_status launch_tile_wide(const KernelSel &k, const char *s, char *d,
-                                  hipStream_t stream)
+/* ---- runtime values -> template instances ------------------------------
+ *
+ * Each kernel family has ONE dispatcher that checks the runtime parameters
+ * and calls a generic callable with compile-time tags; the single-descriptor
+ * launcher and the grouped launcher of a family are the callables, which name
+ * their kernel template and its arguments and nothing else. */
+
+template <typename T> struct Tag { typedef T type; };
+template <int I> using Int = std::integral_constant<int, I>;
+
+/* a kernel launch as an expression, for the dispatchers' callables */
+template <typename K, typename... A>
+static pa_status launch(K kern, dim3 grid, dim3 block, size_t lds,
+                        hipStream_t stream, const A &...args)
 {
-    const CopyDescH &dn = k.d;
-    const int ta = k.ta;
-    if (k.m < 2 || k.ti < 1 || k.tj < 1 || k.pitch < k.ti * k.m)
-        return fail("bad wide-tile selection");
-    DescDev dd = to_dev(dn);
-    int64_t nbatch = 1;
-    for (int a = 1; a < dn.nd; a++)
-        if (a != ta) nbatch *= dn.dims[a];
-    const int64_t nti = (dn.dims[0] + k.ti - 1) / k.ti;
-    const int64_t ntj = (dn.dims[ta] + k.tj - 1) / k.tj;
-    const int64_t nblocks = nti * ntj * nbatch;
-    dim3 grid;
-    pa_status gst = grid2d(nblocks, 256, &grid);
-    if (gst) return gst;
-    const size_t lds = (size_t)k.tj * k.pitch * sizeof(WordT);
-    if (lds > (64u << 10)) return fail("wide tile needs %zu B of LDS", lds);
-    const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + k.m - 1) / k.m);
-    if (k.m == 3)
-        hipLaunchKernelGGL((k_transpose_tile_wide<WordT, 3>), grid,
-                           dim3(64, 4), lds, stream, (const WordT *)s,
-                           (WordT *)d, dd, ta, k.m, magic, k.ti, k.tj,
-                           k.pitch, nti, ntj, nblocks);
-    else
-        hipLaunchKernelGGL((k_transpose_tile_wide<WordT, 0>), grid,
-                           dim3(64, 4), lds, stream, (const WordT *)s,
-                           (WordT *)d, dd, ta, k.m, magic, k.ti, k.tj,
-                           k.pitch, nti, ntj, nblocks);
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
     return 0;
 }
 
-template <typename T>
-static pa_status launch_tile(const KernelSel &k, const char *s, char *d,
-                             hipStream_t stream)
+/* word bytes -> f(Tag<word type>) */
+template <typename F> static pa_status for_word(int W, F &&f)
 {
-    constexpr int TI = 128, TJ = 64, NR = 16;
-    const CopyDescH &dn = k.d;
-    const int ta = k.ta;
-    DescDev dd = to_dev(dn);
-    int64_t nbatch = 1;
-    for (int a = 1; a < dn.nd; a++)
-        if (a != ta) nbatch *= dn.dims[a];
-    const int64_t nti = (dn.dims[0] + TI - 1) / TI;
-    const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
-    const int64_t njc = (ntj + k.sweep - 1) / k.sweep;
-    const int64_t nblocks = nti * njc * nbatch;
-    dim3 grid;
-    pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-    if (gst) return gst;
-#define LAUNCH_TT(JCV)                                                       \
-    hipLaunchKernelGGL((k_transpose_tile<T, TI, TJ, NR, JCV>), grid,         \
-                       dim3(64, NR), 0, stream, (const T *)s, (T *)d, dd,    \
-                       ta, nti, njc, nblocks)
-    if constexpr (sizeof(T) >= 4) {
-        if (k.sweep == 32)
-            LAUNCH_TT(32);
-        else if (k.sweep == 8)
-            LAUNCH_TT(8);
-        else
-            LAUNCH_TT(1);
-    } else {
-        LAUNCH_TT(1);
+    switch (W) {
+    case 16: return f(Tag<uint4>{});
+    case 8: return f(Tag<uint64_t>{});
+    case 4: return f(Tag<uint32_t>{});
+    case 2: return f(Tag<uint16_t>{});
+    case 1: return f(Tag<uint8_t>{});
+    default: return fail("bad word width %d", W);
     }
-#undef LAUNCH_TT
-    return 0;
 }
 
-template <typename T>
-static pa_status launch_tile_pk(const KernelSel &k, const char *s, char *d,
-                                hipStream_t stream)
+/* sweep depth -> f(Int<JCHUNK>), the depths sweep_depth() hands out */
+template <typename F> static pa_status for_sweep(int sweep, F &&f)
 {
-    constexpr int TI = 128, TJ = 128, NT = 256;
-    const CopyDescH &dn = k.d;
-    const int ta = k.ta;
-    DescDev dd = to_dev(dn);
+    return sweep == 32 ? f(Int<32>{}) : sweep == 8 ? f(Int<8>{}) : f(Int<1>{});
+}
+
+/* scalars per access of a linear kernel -> f(Int<V>): the powers of two up
+ * to VMAX = 16 / (widest scalar), so V == 4 exists only where that scalar
+ * has 4 bytes */
+template <int VMAX, typename F> static pa_status for_vec(int V, F &&f)
+{
+    if constexpr (VMAX >= 4)
+        if (V == 4) return f(Int<4>{});
+    if constexpr (VMAX >= 2)
+        if (V == 2) return f(Int<2>{});
+    if (V == 1) return f(Int<1>{});
+    return fail("bad vector width %d", V);
+}
+
+/* scalars per element of a tile kernel -> f(Int<N>), N in LO..4 */
+template <int LO, typename F> static pa_status for_count(int n, F &&f)
+{
+    switch (n) {
+    case 1:
+        if constexpr (LO <= 1) return f(Int<1>{});
+        break;
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    case 4: return f(Int<4>{});
+    }
+    return fail("bad component count %d", n);
+}
+
+/* workgroups of one launch, and the tile counts the tile kernels take */
+struct Grid {
+    int64_t nti = 0, njc = 0, nblocks = 0;
+};
+
+/* the grid of a copy selection: what launch_sel() launches and what a stage
+ * table adds up */
+static Grid sel_grid(const KernelSel &k)
+{
+    const CopyDescH &w = k.d;
+    Grid g;
+    int ti = 0, tj = 0;
+    switch (k.kind) {
+    case PA_KERNEL_NONE:
+        return g;
+    case PA_KERNEL_COPY_1D:
+    case PA_KERNEL_COPY_1D_NT:
+    case PA_KERNEL_LINEAR:
+        g.nblocks = grid_exact(w.total, 256);
+        return g;
+    case PA_KERNEL_GENERIC:
+        g.nblocks = grid_for(w.total, 256);
+        return g;
+    case PA_KERNEL_TILE:
+        ti = k.word == 16 ? 32 : 128;
+        tj = k.word == 16 ? 32 : 64;
+        break;
+    case PA_KERNEL_TILE_VS:
+        ti = 64;
+        tj = 128;
+        break;
+    case PA_KERNEL_TILE_PK:
+        ti = tj = 128;
+        break;
+    default: /* PA_KERNEL_TILE_WIDE */
+        ti = k.ti;
+        tj = k.tj;
+        break;
+    }
     int64_t nbatch = 1;
-    for (int a = 1; a < dn.nd; a++)
-        if (a != ta) nbatch *= dn.dims[a];
-    const int64_t nti = (dn.dims[0] + TI - 1) / TI;
-    const int64_t ntj = (dn.dims[ta] + TJ - 1) / TJ;
-    const int64_t nblocks = nti * ntj * nbatch;
-    dim3 grid;
-    pa_status gst = grid2d(nblocks, NT, &grid);
-    if (gst) return gst;
-    hipLaunchKernelGGL((k_transpose_tile_pk<T, TI, TJ, NT>), grid, dim3(NT),
-                       0, stream, (const T *)s, (T *)d, dd, ta, nti, ntj,
-                       nblocks);
-    return 0;
+    for (int a = 1; a < w.nd; a++)
+        if (a != k.ta) nbatch *= w.dims[a];
+    const int64_t ntj = (w.dims[k.ta] + tj - 1) / tj;
+    g.nti = (w.dims[0] + ti - 1) / ti;
+    g.njc = (ntj + k.sweep - 1) / k.sweep;
+    g.nblocks = g.nti * g.njc * nbatch;
+    return g;
 }
 
 static pa_status launch_sel(const KernelSel &k, const void *src, void *dst,
                             hipStream_t stream)
 {
-    const char *s = (const char *)src;
-    char *d = (char *)dst;
+    if (k.kind == PA_KERNEL_NONE) return 0;
     const CopyDescH &w = k.d;
-    const int W = k.word;
-    pa_status st = 0;
-
-    switch (k.kind) {
-    case PA_KERNEL_NONE:
-        return 0;
-    case PA_KERNEL_COPY_1D:
-    case PA_KERNEL_COPY_1D_NT: {
-        dim3 blocks;
-        pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
-        if (gst) return gst;
-        if (k.kind == PA_KERNEL_COPY_1D_NT)
-            hipLaunchKernelGGL(k_copy_1d_nt, blocks, dim3(256),
-                               0, stream, (const uint4 *)s + w.soff,
-                               (uint4 *)d + w.doff, w.total);
-        else if (W == 16)
-            hipLaunchKernelGGL(k_copy_1d<uint4>, blocks, dim3(256),
-                               0, stream, (const uint4 *)s + w.soff,
-                               (uint4 *)d + w.doff, w.total);
-        else if (W == 8)
-            hipLaunchKernelGGL(k_copy_1d<uint64_t>, blocks,
-                               dim3(256), 0, stream,
-                               (const uint64_t *)s + w.soff,
-                               (uint64_t *)d + w.doff, w.total);
-        else if (W == 4)
-            hipLaunchKernelGGL(k_copy_1d<uint32_t>, blocks,
-                               dim3(256), 0, stream,
-                               (const uint32_t *)s + w.soff,
-                               (uint32_t *)d + w.doff, w.total);
-        else if (W == 2)
-            hipLaunchKernelGGL(k_copy_1d<uint16_t>, blocks,
-                               dim3(256), 0, stream,
-                               (const uint16_t *)s + w.soff,
-                               (uint16_t *)d + w.doff, w.total);
-        else
-            hipLaunchKernelGGL(k_copy_1d<uint8_t>, blocks, dim3(256),
-                               0, stream, (const uint8_t *)s + w.soff,
-                               (uint8_t *)d + w.doff, w.total);
-        break;
-    }
-    case PA_KERNEL_LINEAR: {
-        DescDev dd = to_dev(w);
-        dim3 blocks;
-        pa_status gst = grid2d(grid_exact(w.total, 256), 256, &blocks);
-        if (gst) return gst;
-        if (W == 16)
-            hipLaunchKernelGGL(k_copy_linear<uint4>, blocks,
-                               dim3(256), 0, stream, (const uint4 *)s,
-                               (uint4 *)d, dd);
-        else if (W == 8)
-            hipLaunchKernelGGL(k_copy_linear<uint64_t>, blocks,
-                               dim3(256), 0, stream, (const uint64_t *)s,
-                               (uint64_t *)d, dd);
-        else if (W == 4)
-            hipLaunchKernelGGL(k_copy_linear<uint32_t>, blocks,
-                               dim3(256), 0, stream, (const uint32_t *)s,
-                               (uint32_t *)d, dd);
-        else if (W == 2)
-            hipLaunchKernelGGL(k_copy_linear<uint16_t>, blocks,
-                               dim3(256), 0, stream, (const uint16_t *)s,
-                               (uint16_t *)d, dd);
-        else
-            hipLaunchKernelGGL(k_copy_linear<uint8_t>, blocks,
-                               dim3(256), 0, stream, (const uint8_t *)s,
-                               (uint8_t *)d, dd);
-        break;
-    }
-    case PA_KERNEL_TILE_VS: {
-        constexpr int TI = 64, TJ = 128, NR = 16;
-        const int ta = k.ta;
-        DescDev dd = to_dev(w);
-        int64_t nbatch = 1;
-        for (int a = 1; a < w.nd; a++)
-            if (a != ta) nbatch *= w.dims[a];
-        const int64_t nti = (w.dims[0] + TI - 1) / TI;
-        const int64_t ntj = (w.dims[ta] + TJ - 1) / TJ;
-        const int64_t njc = (ntj + k.sweep - 1) / k.sweep;
-        const int64_t nblocks = nti * njc * nbatch;
+    const Grid g = sel_grid(k);
+    const int ta = k.ta;
+    pa_status st = for_word(k.word, [&](auto tag) -> pa_status {
+        using T = typename decltype(tag)::type;
+        const T *s = (const T *)src;
+        T *d = (T *)dst;
         dim3 grid;
-        pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-        if (gst) return gst;
-#define LAUNCH_VS(JCV)                                                       \
-    do {                                                                     \
-        if (k.stream)                                                        \
-            hipLaunchKernelGGL(                                              \
-                (k_transpose_tile_vs_nt<uint64_t, TI, TJ, NR, JCV>), grid,   \
-                dim3(64, NR), 0, stream, (const uint64_t *)s,                \
-                (uint64_t *)d, dd, ta, nti, njc, nblocks);                   \
-        else                                                                 \
-            hipLaunchKernelGGL(                                              \
-                (k_transpose_tile_vs<uint64_t, TI, TJ, NR, JCV>), grid,      \
-                dim3(64, NR), 0, stream, (const uint64_t *)s,                \
-                (uint64_t *)d, dd, ta, nti, njc, nblocks);                   \
-    } while (0)
-        if (k.sweep == 32)
-            LAUNCH_VS(32);
-        else if (k.sweep == 8)
-            LAUNCH_VS(8);
-        else
-            LAUNCH_VS(1);
-#undef LAUNCH_VS
-        break;
-    }
-    case PA_KERNEL_TILE:
-        if (W == 16) {
-            constexpr int TI = 32, TJ = 32, NR = 8, JC = 1;
-            const int ta = k.ta;
-            DescDev dd = to_dev(w);
-            int64_t nbatch = 1;
-            for (int a = 1; a < w.nd; a++)
-                if (a != ta) nbatch *= w.dims[a];
-            const int64_t nti = (w.dims[0] + TI - 1) / TI;
-            const int64_t ntj = (w.dims[ta] + TJ - 1) / TJ;
-            const int64_t nblocks = nti * ntj * nbatch;
-            dim3 grid;
-            pa_status gst = grid2d(nblocks, 64 * NR, &grid);
-            if (gst) return gst;
-            hipLaunchKernelGGL((k_transpose_tile<uint4, TI, TJ, NR, JC>),
-                               grid, dim3(64, NR), 0, stream,
-                               (const uint4 *)s, (uint4 *)d, dd, ta, nti, ntj,
-                               nblocks);
-        } else if (W == 8)
-            st = launch_tile<uint64_t>(k, s, d, stream);
-        else if (W == 4)
-            st = launch_tile<uint32_t>(k, s, d, stream);
-        else if (W == 2)
-            st = launch_tile<uint16_t>(k, s, d, stream);
-        else
-            st = launch_tile<uint8_t>(k, s, d, stream);
-        if (st) return st;
-        break;
-    case PA_KERNEL_TILE_PK:
-        st = W == 2 ? launch_tile_pk<uint16_t>(k, s, d, stream)
-                    : launch_tile_pk<uint8_t>(k, s, d, stream);
-        if (st) return st;
-        break;
-    case PA_KERNEL_TILE_WIDE:
-        st = W == 16  ? launch_tile_wide<uint4>(k, s, d, stream)
-             : W == 8 ? launch_tile_wide<uint64_t>(k, s, d, stream)
-             : W == 4 ? launch_tile_wide<uint32_t>(k, s, d, stream)
-             : W == 2 ? launch_tile_wide<uint16_t>(k, s, d, stream)
-                      : launch_tile_wide<uint8_t>(k, s, d, stream);
-        if (st) return st;
-        break;
-    case PA_KERNEL_GENERIC: {
-        DescDev dd = to_dev(w);
-        const dim3 blocks(grid_for(w.total, 256)); /* grid-stride kernel */
-        if (W == 16)
-            hipLaunchKernelGGL(k_copy_generic<uint4>, blocks, dim3(256),
-                               0, stream, (const uint4 *)s, (uint4 *)d, dd);
-        else if (W == 8)
-            hipLaunchKernelGGL(k_copy_generic<uint64_t>, blocks,
-                               dim3(256), 0, stream, (const uint64_t *)s,
-                               (uint64_t *)d, dd);
-        else if (W == 4)
-            hipLaunchKernelGGL(k_copy_generic<uint32_t>, blocks,
-                               dim3(256), 0, stream, (const uint32_t *)s,
-                               (uint32_t *)d, dd);
-        else if (W == 2)
-            hipLaunchKernelGGL(k_copy_generic<uint16_t>, blocks,
-                               dim3(256), 0, stream, (const uint16_t *)s,
-                               (uint16_t *)d, dd);
-        else
-            hipLaunchKernelGGL(k_copy_generic<uint8_t>, blocks,
-                               dim3(256), 0, stream, (const uint8_t *)s,
-                               (uint8_t *)d, dd);
-        break;
-    }
-    default:
-        return fail("bad kernel kind %d", k.kind);
-    }
+        switch (k.kind) {
+        case PA_KERNEL_COPY_1D:
+            if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+            return launch(k_copy_1d<T>, grid, dim3(256), 0, stream,
+                          s + w.soff, d + w.doff, w.total);
+        case PA_KERNEL_COPY_1D_NT:
+            if constexpr (sizeof(T) == 16) {
+                if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+                return launch(k_copy_1d_nt, grid, dim3(256), 0, stream,
+                              s + w.soff, d + w.doff, w.total);
+            }
+            break;
+        case PA_KERNEL_LINEAR:
+            if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+            return launch(k_copy_linear<T>, grid, dim3(256), 0, stream, s, d,
+                          to_dev(w));
+        case PA_KERNEL_GENERIC: /* grid-stride kernel */
+            return launch(k_copy_generic<T>, dim3((uint32_t)g.nblocks),
+                          dim3(256), 0, stream, s, d, to_dev(w));
+        case PA_KERNEL_TILE:
+            /* 16-byte words: 32x32; 4- and 8-byte: 128x64 with a sweep;
+             * 1- and 2-byte: 128x64, one tile per workgroup */
+            if constexpr (sizeof(T) == 16) {
+                if (pa_status gst = grid2d(g.nblocks, 64 * 8, &grid))
+                    return gst;
+                return launch(k_transpose_tile<T, 32, 32, 8, 1>, grid,
+                              dim3(64, 8), 0, stream, s, d, to_dev(w), ta,
+                              g.nti, g.njc, g.nblocks);
+            } else {
+                if (pa_status gst = grid2d(g.nblocks, 64 * 16, &grid))
+                    return gst;
+                if constexpr (sizeof(T) >= 4)
+                    return for_sweep(k.sweep, [&](auto jc) {
+                        return launch(
+                            k_transpose_tile<T, 128, 64, 16,
+                                             decltype(jc)::value>,
+                            grid, dim3(64, 16), 0, stream, s, d, to_dev(w),
+                            ta, g.nti, g.njc, g.nblocks);
+                    });
+                else
+                    return launch(k_transpose_tile<T, 128, 64, 16, 1>, grid,
+                                  dim3(64, 16), 0, stream, s, d, to_dev(w),
+                                  ta, g.nti, g.njc, g.nblocks);
+            }
+        case PA_KERNEL_TILE_VS:
+            if constexpr (sizeof(T) == 8) {
+                if (pa_status gst = grid2d(g.nblocks, 64 * 16, &grid))
+                    return gst;
+                return for_sweep(k.sweep, [&](auto jc) {
+                    constexpr int JC = decltype(jc)::value;
+                    return launch(
+                        k.stream ? k_transpose_tile_vs_nt<T, 64, 128, 16, JC>
+                                 : k_transpose_tile_vs<T, 64, 128, 16, JC>,
+                        grid, dim3(64, 16), 0, stream, s, d, to_dev(w), ta,
+                        g.nti, g.njc, g.nblocks);
+                });
+            }
+            break;
+        case PA_KERNEL_TILE_PK:
+            if constexpr (sizeof(T) <= 2) {
+                if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+                return launch(k_transpose_tile_pk<T, 128, 128, 256>, grid,
+                              dim3(256), 0, stream, s, d, to_dev(w), ta,
+                              g.nti, g.njc, g.nblocks);
+            }
+            break;
+        case PA_KERNEL_TILE_WIDE: {
+            if (k.m < 2 || k.ti < 1 || k.tj < 1 || k.pitch < k.ti * k.m)
+                return fail("bad wide-tile selection");
+            if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+            const size_t lds = (size_t)k.tj * k.pitch * sizeof(T);
+            if (lds > (64u << 10))
+                return fail("wide tile needs %zu B of LDS", lds);
+            const uint32_t magic =
+                (uint32_t)((((uint64_t)1 << 32) + k.m - 1) / k.m);
+            return launch(k.m == 3 ? k_transpose_tile_wide<T, 3>
+                                   : k_transpose_tile_wide<T, 0>,
+                          grid, dim3(64, 4), lds, stream, s, d, to_dev(w), ta,
+                          k.m, magic, k.ti, k.tj, k.pitch, g.nti, g.njc,
+                          g.nblocks);
+        }
+        default:
+            return fail("bad kernel kind %d", k.kind);
+        }
+        return fail("kernel kind %d has no %d-byte word", k.kind, k.word);
+    });
+    if (st) return st;
     HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -2264,21 +2207,17 @@ static pa_status check_wire(int wire, int op, int64_t ncomp)
     return 0;
 }
 
-static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
-                                   int64_t ncomp, const void *src,
-                                   const void *dst, CvtSel *out)
-{
-    if (pa_status st = check_wire(wire, op, ncomp)) return st;
-    *out = CvtSel();
-    out->wire = wire;
-    out->op = op;
-    out->ncomp = (int)ncomp;
-    if (dn.total == 0) return 0;
-    int64_t stored, wsz;
-    wire_sizes(wire, &stored, &wsz);
-    const int64_t ssz = op == PA_WIRE_WIDEN ? wsz : stored;
-    const int64_t dsz = op == PA_WIRE_NARROW ? wsz : stored;
+/* The linear / tile / generic decision shared by the converting and the
+ * scaling selectors, for elements of ncomp scalars of ssz bytes at the source
+ * and dsz bytes at the destination.  Linear: the components join the
+ * contiguous axis and out->d is in units of out->V scalars.  Tile: out->ta is
+ * the destination-contiguous axis; the caller sets the tile shape. */
+enum { SHAPE_LINEAR, SHAPE_TILE, SHAPE_GENERIC };
 
+static int select_shape(const CopyDescH &dn, int64_t ssz, int64_t dsz,
+                        int64_t ncomp, const void *src, const void *dst,
+                        CvtSel *out)
+{
     if (dn.sstr[0] == 1 && dn.dstr[0] == 1) {
         /* scalar units: the components join the contiguous axis */
         CopyDescH w = dn;
@@ -2311,10 +2250,9 @@ static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
         }
         w.total = 1;
         for (int a = 0; a < w.nd; a++) w.total *= w.dims[a];
-        out->kind = PA_KERNEL_CVT_LINEAR;
         out->V = (int)V;
         out->d = w;
-        return 0;
+        return SHAPE_LINEAR;
     }
 
     out->d = dn;
@@ -2323,13 +2261,38 @@ static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
         for (int a = 1; a < dn.nd; a++)
             if (dn.dstr[a] == 1) { ta = a; break; }
     if (ta > 0 && ncomp <= PA_CVT_TILE_MAX_COMP) {
-        out->kind = PA_KERNEL_CVT_TILE;
         out->ta = ta;
+        return SHAPE_TILE;
+    }
+    return SHAPE_GENERIC;
+}
+
+static pa_status select_kernel_cvt(const CopyDescH &dn, int wire, int op,
+                                   int64_t ncomp, const void *src,
+                                   const void *dst, CvtSel *out)
+{
+    if (pa_status st = check_wire(wire, op, ncomp)) return st;
+    *out = CvtSel();
+    out->wire = wire;
+    out->op = op;
+    out->ncomp = (int)ncomp;
+    if (dn.total == 0) return 0;
+    int64_t stored, wsz;
+    wire_sizes(wire, &stored, &wsz);
+    const int64_t ssz = op == PA_WIRE_WIDEN ? wsz : stored;
+    const int64_t dsz = op == PA_WIRE_NARROW ? wsz : stored;
+    switch (select_shape(dn, ssz, dsz, ncomp, src, dst, out)) {
+    case SHAPE_LINEAR:
+        out->kind = PA_KERNEL_CVT_LINEAR;
+        break;
+    case SHAPE_TILE:
+        out->kind = PA_KERNEL_CVT_TILE;
         out->ti = cvt_tile_ti((int)ncomp);
         out->tj = CVT_TILE_TJ;
-        return 0;
+        break;
+    default:
+        out->kind = PA_KERNEL_CVT_GENERIC;
     }
-    out->kind = PA_KERNEL_CVT_GENERIC;
     return 0;
 }
 
@@ -2360,95 +2323,87 @@ static int64_t cvt_grid(const CvtSel &k, int64_t *nti, int64_t *ntj)
     }
 }
 
-/* expand F(WIRE, OP) for the runtime pair (wire, op) */
-#define CVT_FOR_WIRE_OP(wire, op, F)                                         \
-    switch ((wire) * 3 + (op)) {                                             \
-    case 3: F(1, 0); break;                                                  \
-    case 4: F(1, 1); break;                                                  \
-    case 5: F(1, 2); break;                                                  \
-    case 6: F(2, 0); break;                                                  \
-    case 7: F(2, 1); break;                                                  \
-    case 8: F(2, 2); break;                                                  \
-    case 9: F(3, 0); break;                                                  \
-    case 10: F(3, 1); break;                                                 \
-    case 11: F(3, 2); break;                                                 \
-    default: return fail("bad wire pair %d / op %d", (wire), (op));          \
-    }
-
-/* V starts at 16 / (widest scalar): 4 only exists for the f32 pairs */
-template <int W, int O>
-static void launch_cvt_linear(int V, dim3 grid, hipStream_t stream,
-                              const void *src, void *dst, const DescDev &dd)
+/* the launch grid of a converting or scaling kind over nblocks workgroups:
+ * 256 threads (linear), 64 x 16 (tile), a 1-D grid-stride grid (generic) */
+static pa_status cvt_dim(int kind, int64_t nblocks, dim3 *grid)
 {
-    if constexpr (W != PA_WIRE_F64_F32) {
-        if (V == 4) {
-            hipLaunchKernelGGL((k_cvt_linear<W, O, 4>), grid, dim3(256), 0,
-                               stream, src, dst, dd);
-            return;
-        }
+    switch (kind) {
+    case PA_KERNEL_CVT_LINEAR:
+    case PA_KERNEL_SCALE_LINEAR:
+        return grid2d(nblocks, 256, grid);
+    case PA_KERNEL_CVT_TILE:
+    case PA_KERNEL_SCALE_TILE:
+        return grid2d(nblocks, 64 * 16, grid);
+    default:
+        *grid = dim3((uint32_t)nblocks);
+        return 0;
     }
-    if (V == 2)
-        hipLaunchKernelGGL((k_cvt_linear<W, O, 2>), grid, dim3(256), 0,
-                           stream, src, dst, dd);
-    else
-        hipLaunchKernelGGL((k_cvt_linear<W, O, 1>), grid, dim3(256), 0,
-                           stream, src, dst, dd);
+}
+
+/* The converting family: (wire, op), then V (linear) or the component count
+ * (tile), become lin(Int<WIRE>, Int<OP>, Int<V>), tile(Int<WIRE>, Int<OP>,
+ * Int<NC>) or gen(Int<WIRE>, Int<OP>). */
+template <typename L, typename T, typename G>
+static pa_status for_cvt(const CvtSel &k, L &&lin, T &&tile, G &&gen)
+{
+    auto shape = [&](auto w, auto o) -> pa_status {
+        /* the widest scalar of the pair is the stored one */
+        constexpr int VMAX = decltype(w)::value == PA_WIRE_F64_F32 ? 2 : 4;
+        switch (k.kind) {
+        case PA_KERNEL_CVT_LINEAR:
+            return for_vec<VMAX>(k.V, [&](auto v) { return lin(w, o, v); });
+        case PA_KERNEL_CVT_TILE:
+            return for_count<1>(k.ncomp,
+                                [&](auto nc) { return tile(w, o, nc); });
+        case PA_KERNEL_CVT_GENERIC:
+            return gen(w, o);
+        default:
+            return fail("bad converting kernel kind %d", k.kind);
+        }
+    };
+    switch (k.wire * 3 + k.op) {
+    case 3: return shape(Int<1>{}, Int<0>{});
+    case 4: return shape(Int<1>{}, Int<1>{});
+    case 5: return shape(Int<1>{}, Int<2>{});
+    case 6: return shape(Int<2>{}, Int<0>{});
+    case 7: return shape(Int<2>{}, Int<1>{});
+    case 8: return shape(Int<2>{}, Int<2>{});
+    case 9: return shape(Int<3>{}, Int<0>{});
+    case 10: return shape(Int<3>{}, Int<1>{});
+    case 11: return shape(Int<3>{}, Int<2>{});
+    default: return fail("bad wire pair %d / op %d", k.wire, k.op);
+    }
 }
 
 static pa_status launch_cvt_sel(const CvtSel &k, const void *src, void *dst,
                                 hipStream_t stream)
 {
     if (k.kind == PA_KERNEL_NONE) return 0;
+    /* the tile shape the kernel assumes; checked here because it does not
+     * depend on the instance (the scaling tile's does: see its tile lambda) */
+    if (k.kind == PA_KERNEL_CVT_TILE &&
+        (k.ta < 1 || k.ti != cvt_tile_ti(k.ncomp) || k.tj != CVT_TILE_TJ))
+        return fail("bad converting-tile selection");
     int64_t nti, ntj;
     const int64_t nblocks = cvt_grid(k, &nti, &ntj);
-    DescDev dd = to_dev(k.d);
+    const DescDev dd = to_dev(k.d);
     dim3 grid;
-    switch (k.kind) {
-    case PA_KERNEL_CVT_LINEAR: {
-        if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
-        if (k.V != 1 && k.V != 2 && !(k.V == 4 && k.wire != PA_WIRE_F64_F32))
-            return fail("bad vector width %d", k.V);
-#define CVT_LIN(W, O) launch_cvt_linear<W, O>(k.V, grid, stream, src, dst, dd)
-        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_LIN)
-#undef CVT_LIN
-        break;
-    }
-    case PA_KERNEL_CVT_TILE: {
-        if (k.ta < 1 || k.ncomp > PA_CVT_TILE_MAX_COMP ||
-            k.ti != cvt_tile_ti(k.ncomp) || k.tj != CVT_TILE_TJ)
-            return fail("bad converting-tile selection");
-        if (pa_status gst = grid2d(nblocks, 64 * 16, &grid)) return gst;
-#define CVT_TILE_NC(W, O, NC)                                                \
-    hipLaunchKernelGGL((k_cvt_tile<W, O, NC>), grid, dim3(64, 16), 0,        \
-                       stream, src, dst, dd, k.ta, nti, ntj, nblocks)
-#define CVT_TILE(W, O)                                                       \
-    do {                                                                     \
-        if (k.ncomp == 1)                                                    \
-            CVT_TILE_NC(W, O, 1);                                            \
-        else if (k.ncomp == 2)                                               \
-            CVT_TILE_NC(W, O, 2);                                            \
-        else if (k.ncomp == 3)                                               \
-            CVT_TILE_NC(W, O, 3);                                            \
-        else                                                                 \
-            CVT_TILE_NC(W, O, 4);                                            \
-    } while (0)
-        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_TILE)
-#undef CVT_TILE
-#undef CVT_TILE_NC
-        break;
-    }
-    case PA_KERNEL_CVT_GENERIC: {
-        grid = dim3((uint32_t)nblocks); /* grid-stride kernel */
-#define CVT_GEN(W, O)                                                        \
-    hipLaunchKernelGGL((k_cvt_generic<W, O>), grid, dim3(256), 0, stream,    \
-                       src, dst, dd, k.ncomp)
-        CVT_FOR_WIRE_OP(k.wire, k.op, CVT_GEN)
-#undef CVT_GEN
-        break;
-    }
-    default:
-        return fail("bad converting kernel kind %d", k.kind);
-    }
+    if (pa_status gst = cvt_dim(k.kind, nblocks, &grid)) return gst;
+    pa_status st = for_cvt(
+        k,
+        [&](auto w, auto o, auto v) {
+            return launch(k_cvt_linear<w, o, v>, grid, dim3(256), 0, stream,
+                          src, dst, dd);
+        },
+        [&](auto w, auto o, auto nc) {
+            return launch(k_cvt_tile<w, o, nc>, grid, dim3(64, 16), 0, stream,
+                          src, dst, dd, k.ta, nti, ntj, nblocks);
+        },
+        [&](auto w, auto o) {
+            return launch(k_cvt_generic<w, o>, grid, dim3(256), 0, stream,
+                          src, dst, dd, k.ncomp);
+        });
+    if (st) return st;
     HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -2495,127 +2450,78 @@ static pa_status select_kernel_scale(const CopyDescH &dn, int scalar,
     out->ncomp = (int)nscal;
     if (dn.total == 0) return 0;
     const int64_t sz = scalar_bytes(scalar);
-
-    if (dn.sstr[0] == 1 && dn.dstr[0] == 1) {
-        /* scalar units: the components join the contiguous axis */
-        CopyDescH w = dn;
-        w.dims[0] *= nscal;
-        w.soff *= nscal;
-        w.doff *= nscal;
-        for (int a = 1; a < w.nd; a++) {
-            w.sstr[a] *= nscal;
-            w.dstr[a] *= nscal;
-        }
-        int64_t V = 16 / sz;
-        auto ok = [&](int64_t v) {
-            if (w.dims[0] % v || w.soff % v || w.doff % v) return false;
-            if ((uintptr_t)src % (uintptr_t)(v * sz)) return false;
-            if ((uintptr_t)dst % (uintptr_t)(v * sz)) return false;
-            for (int a = 1; a < w.nd; a++)
-                if (w.sstr[a] % v || w.dstr[a] % v) return false;
-            return true;
-        };
-        while (V > 1 && !ok(V)) V >>= 1;
-        w.dims[0] /= V;
-        w.soff /= V;
-        w.doff /= V;
-        for (int a = 1; a < w.nd; a++) {
-            w.sstr[a] /= V;
-            w.dstr[a] /= V;
-        }
-        w.total = 1;
-        for (int a = 0; a < w.nd; a++) w.total *= w.dims[a];
+    switch (select_shape(dn, sz, sz, nscal, src, dst, out)) {
+    case SHAPE_LINEAR:
         out->kind = PA_KERNEL_SCALE_LINEAR;
-        out->V = (int)V;
-        out->d = w;
-        return 0;
-    }
-
-    out->d = dn;
-    int ta = -1;
-    if (dn.sstr[0] == 1)
-        for (int a = 1; a < dn.nd; a++)
-            if (dn.dstr[a] == 1) { ta = a; break; }
-    if (ta > 0 && nscal <= PA_CVT_TILE_MAX_COMP) {
+        break;
+    case SHAPE_TILE:
         out->kind = PA_KERNEL_SCALE_TILE;
-        out->ta = ta;
         out->ti = scalar == PA_SCALAR_F32 ? scale_tile_ti<float>((int)nscal)
                                           : scale_tile_ti<double>((int)nscal);
         out->tj = SCALE_TILE_TJ;
-        return 0;
+        break;
+    default:
+        out->kind = PA_KERNEL_SCALE_GENERIC;
     }
-    out->kind = PA_KERNEL_SCALE_GENERIC;
     return 0;
 }
 
-/* the single-descriptor launches of scalar type S; a = S(alpha) */
-template <typename S>
-static pa_status launch_scale_sel_t(const CvtSel &k, const void *src,
-                                    void *dst, S a, hipStream_t stream)
+/* The scaling family: the scalar type, then V (linear) or the scalars per
+ * element (tile), become lin(a, Int<V>), tile(a, Int<NC>) or gen(a), with
+ * a = S(alpha) carrying the scalar type S. */
+template <typename L, typename T, typename G>
+static pa_status for_scale(const CvtSel &k, double alpha, L &&lin, T &&tile,
+                           G &&gen)
 {
-    int64_t nti, ntj;
-    const int64_t nblocks = cvt_grid(k, &nti, &ntj);
-    DescDev dd = to_dev(k.d);
-    dim3 grid;
-    switch (k.kind) {
-    case PA_KERNEL_SCALE_LINEAR: {
-        if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
-#define SCALE_LIN(V)                                                         \
-    hipLaunchKernelGGL((k_scale_linear<S, V>), grid, dim3(256), 0, stream,   \
-                       src, dst, dd, a)
-        /* V starts at 16 / sizeof(S): 4 only exists for f32 */
-        if (k.V != 1 && k.V != 2 && !(k.V == 4 && sizeof(S) == 4))
-            return fail("bad vector width %d", k.V);
-        if constexpr (sizeof(S) == 4) {
-            if (k.V == 4) SCALE_LIN(4);
+    auto shape = [&](auto a) -> pa_status {
+        constexpr int VMAX = 16 / (int)sizeof(a);
+        switch (k.kind) {
+        case PA_KERNEL_SCALE_LINEAR:
+            return for_vec<VMAX>(k.V, [&](auto v) { return lin(a, v); });
+        case PA_KERNEL_SCALE_TILE:
+            return for_count<1>(k.ncomp, [&](auto nc) { return tile(a, nc); });
+        case PA_KERNEL_SCALE_GENERIC:
+            return gen(a);
+        default:
+            return fail("bad scaling kernel kind %d", k.kind);
         }
-        if (k.V == 2)
-            SCALE_LIN(2);
-        else if (k.V == 1)
-            SCALE_LIN(1);
-#undef SCALE_LIN
-        break;
-    }
-    case PA_KERNEL_SCALE_TILE: {
-        if (k.ta < 1 || k.ncomp < 1 || k.ncomp > PA_CVT_TILE_MAX_COMP ||
-            k.ti != scale_tile_ti<S>(k.ncomp) || k.tj != SCALE_TILE_TJ)
-            return fail("bad scaling-tile selection");
-        if (pa_status gst = grid2d(nblocks, 64 * 16, &grid)) return gst;
-#define SCALE_TILE_NC(NC)                                                    \
-    hipLaunchKernelGGL((k_scale_tile<S, NC>), grid, dim3(64, 16), 0, stream, \
-                       src, dst, dd, k.ta, nti, ntj, nblocks, a)
-        if (k.ncomp == 1)
-            SCALE_TILE_NC(1);
-        else if (k.ncomp == 2)
-            SCALE_TILE_NC(2);
-        else if (k.ncomp == 3)
-            SCALE_TILE_NC(3);
-        else
-            SCALE_TILE_NC(4);
-#undef SCALE_TILE_NC
-        break;
-    }
-    case PA_KERNEL_SCALE_GENERIC:
-        grid = dim3((uint32_t)nblocks); /* grid-stride kernel */
-        hipLaunchKernelGGL((k_scale_generic<S>), grid, dim3(256), 0, stream,
-                           src, dst, dd, k.ncomp, a);
-        break;
-    default:
-        return fail("bad scaling kernel kind %d", k.kind);
-    }
-    HIP_CHECK(hipGetLastError());
-    return 0;
+    };
+    if (k.scalar == PA_SCALAR_F32) return shape((float)alpha);
+    if (k.scalar == PA_SCALAR_F64) return shape(alpha);
+    return fail("bad scalar type %d", k.scalar);
 }
 
 static pa_status launch_scale_sel(const CvtSel &k, const void *src, void *dst,
                                   double alpha, hipStream_t stream)
 {
     if (k.kind == PA_KERNEL_NONE) return 0;
-    if (k.scalar == PA_SCALAR_F32)
-        return launch_scale_sel_t<float>(k, src, dst, (float)alpha, stream);
-    if (k.scalar == PA_SCALAR_F64)
-        return launch_scale_sel_t<double>(k, src, dst, alpha, stream);
-    return fail("bad scalar type %d", k.scalar);
+    int64_t nti, ntj;
+    const int64_t nblocks = cvt_grid(k, &nti, &ntj);
+    const DescDev dd = to_dev(k.d);
+    dim3 grid;
+    if (pa_status gst = cvt_dim(k.kind, nblocks, &grid)) return gst;
+    pa_status st = for_scale(
+        k, alpha,
+        [&](auto a, auto v) {
+            return launch(k_scale_linear<decltype(a), v>, grid, dim3(256), 0,
+                          stream, src, dst, dd, a);
+        },
+        [&](auto a, auto nc) -> pa_status {
+            /* the tile shape the kernel assumes depends on the scalar type,
+             * so the check sits where that type is known */
+            if (k.ta < 1 || k.ti != scale_tile_ti<decltype(a)>(k.ncomp) ||
+                k.tj != SCALE_TILE_TJ)
+                return fail("bad scaling-tile selection");
+            return launch(k_scale_tile<decltype(a), nc>, grid, dim3(64, 16),
+                          0, stream, src, dst, dd, k.ta, nti, ntj, nblocks, a);
+        },
+        [&](auto a) {
+            return launch(k_scale_generic<decltype(a)>, grid, dim3(256), 0,
+                          stream, src, dst, dd, k.ncomp, a);
+        });
+    if (st) return st;
+    HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 /* ---- split / join copies: selection and launch ------------------------ */
@@ -2720,87 +2626,49 @@ static pa_status select_kernel_soa(const CopyDescH &dn, int64_t ssz, int n,
     return 0;
 }
 
-/* M is the multiplier policy: SoaNoMul for a plain call, SoaMul<R> holding
- * a = R(alpha) for a scaled one, S being one or two R.  It picks the
- * instantiation and rides in the pointer struct; everything else about the
- * launch is the same code for both. */
-template <typename S, typename M, int DIR, int N>
-static pa_status launch_soa_n(const SoaSel &k, void *aos, void *const *fields,
-                              const M &m, hipStream_t stream)
+/* workgroups per component of the grid-stride generic split / join kernel */
+static int soa_generic_gx(const SoaSel &k)
+{
+    return grid_for(k.d.total, 256);
+}
+
+/* the grid of a split / join selection: what launch_soa_sel() launches and
+ * what a stage table adds up.  The generic kernel's count is over all n
+ * components (its launches spread them over blockIdx.z). */
+static Grid soa_grid(const SoaSel &k)
+{
+    Grid g;
+    switch (k.kind) {
+    case PA_KERNEL_SOA_LINEAR:
+        g.nblocks = grid_exact(k.d.total, 256);
+        break;
+    case PA_KERNEL_SOA_GENERIC:
+        g.nblocks = (int64_t)soa_generic_gx(k) * k.n;
+        break;
+    case PA_KERNEL_SOA_TILE: {
+        int64_t nbatch = 1;
+        for (int a = 1; a < k.d.nd; a++)
+            if (a != k.ta) nbatch *= k.d.dims[a];
+        g.nti = (k.d.dims[0] + k.ti - 1) / k.ti;
+        g.njc = (k.d.dims[k.ta] + k.tj - 1) / k.tj;
+        g.nblocks = g.nti * g.njc * nbatch;
+        break;
+    }
+    default:
+        break;
+    }
+    return g;
+}
+
+/* the kernel argument holding the multiplier policy and N field pointers,
+ * the first nc of them set */
+template <int N, typename M>
+static SoaPtrs<N, M> soa_ptrs(const M &m, void *const *fields, int nc)
 {
     SoaPtrs<N, M> f;
     static_cast<M &>(f) = m;
-    for (int c = 0; c < N; c++) f.p[c] = fields[c];
-    DescDev dd = to_dev(k.d);
-    dim3 grid;
-    if (k.kind == PA_KERNEL_SOA_LINEAR) {
-        if (pa_status gst = grid2d(grid_exact(k.d.total, 256), 256, &grid))
-            return gst;
-        constexpr int VMAX = 16 / (int)sizeof(S);
-#define SOA_LIN(VV)                                                          \
-    hipLaunchKernelGGL((k_soa_linear<S, DIR, N, VV, M>), grid, dim3(256), 0, \
-                       stream, aos, f, dd)
-        if (k.V < 1 || k.V > VMAX) return fail("bad vector width %d", k.V);
-        if constexpr (VMAX >= 4) {
-            if (k.V == 4) { SOA_LIN(4); return 0; }
-        }
-        if constexpr (VMAX >= 2) {
-            if (k.V == 2) { SOA_LIN(2); return 0; }
-        }
-        if (k.V != 1) return fail("bad vector width %d", k.V);
-        SOA_LIN(1);
-#undef SOA_LIN
-        return 0;
-    }
-    /* PA_KERNEL_SOA_TILE */
-    const CopyDescH &dn = k.d;
-    const int64_t row = DIR == PA_SOA_SPLIT ? (int64_t)k.ti * N : k.ti;
-    if (k.ta < 1 || k.ti < 1 || k.tj != PA_SOA_TILE_TJ || k.pitch < row ||
-        (DIR == PA_SOA_JOIN && k.plane < k.tj * k.pitch))
-        return fail("bad split/join tile selection");
-    int64_t nbatch = 1;
-    for (int a = 1; a < dn.nd; a++)
-        if (a != k.ta) nbatch *= dn.dims[a];
-    const int64_t nti = (dn.dims[0] + k.ti - 1) / k.ti;
-    const int64_t ntj = (dn.dims[k.ta] + k.tj - 1) / k.tj;
-    const int64_t nblocks = nti * ntj * nbatch;
-    if (pa_status gst = grid2d(nblocks, 256, &grid)) return gst;
-    const size_t lds = sizeof(S) * (DIR == PA_SOA_SPLIT
-                                        ? (size_t)k.tj * k.pitch
-                                        : (size_t)N * k.plane);
-    if (lds > (64u << 10))
-        return fail("split/join tile needs %zu B of LDS", lds);
-    hipLaunchKernelGGL((k_soa_tile<S, DIR, N, M>), grid, dim3(64, 4), lds,
-                       stream, aos, f, dd, k.ta, k.ti, k.pitch, k.plane, nti,
-                       ntj, nblocks);
-    return 0;
-}
-
-template <typename S, typename M, int DIR>
-static pa_status launch_soa_t(const SoaSel &k, void *aos, void *const *fields,
-                              const M &m, hipStream_t stream)
-{
-    if (k.kind == PA_KERNEL_SOA_GENERIC) {
-        /* grid-stride kernel, at most PA_SOA_GENERIC_PTRS fields a launch */
-        DescDev dd = to_dev(k.d);
-        const int gx = grid_for(k.d.total, 256);
-        for (int c0 = 0; c0 < k.n; c0 += PA_SOA_GENERIC_PTRS) {
-            const int nc = std::min(k.n - c0, PA_SOA_GENERIC_PTRS);
-            SoaPtrs<PA_SOA_GENERIC_PTRS, M> f;
-            static_cast<M &>(f) = m;
-            for (int c = 0; c < PA_SOA_GENERIC_PTRS; c++)
-                f.p[c] = c < nc ? fields[c0 + c] : nullptr;
-            hipLaunchKernelGGL((k_soa_generic<S, DIR, M>), dim3(gx, 1, nc),
-                               dim3(256), 0, stream, aos, f, dd, k.n, c0);
-        }
-        return 0;
-    }
-    switch (k.n) {
-    case 2: return launch_soa_n<S, M, DIR, 2>(k, aos, fields, m, stream);
-    case 3: return launch_soa_n<S, M, DIR, 3>(k, aos, fields, m, stream);
-    case 4: return launch_soa_n<S, M, DIR, 4>(k, aos, fields, m, stream);
-    default: return fail("bad split/join selection: n = %d", k.n);
-    }
+    for (int c = 0; c < N; c++) f.p[c] = c < nc ? fields[c] : nullptr;
+    return f;
 }
 
 /* The scalar sizes a scale of real type `scalar` applies to: one scalar or
@@ -2816,6 +2684,62 @@ static pa_status check_soa_scale(int64_t ssz, int scalar, double alpha)
     return 0;
 }
 
+/* The split / join family: the scalar word S, the multiplier policy, the
+ * direction and N, then V (linear) or the tile's LDS bytes, become
+ * lin(Tag<S>, m, Int<DIR>, Int<N>, Int<V>), tile(Tag<S>, m, Int<DIR>, Int<N>,
+ * lds) or gen(Tag<S>, m, Int<DIR>).  m is the policy value: SoaNoMul for a
+ * plain call (scalar == 0), SoaMul<R> holding R(alpha) for a scaled one, S
+ * being one or two R. */
+template <typename L, typename T, typename G>
+static pa_status for_soa(const SoaSel &k, int scalar, double alpha, L &&lin,
+                         T &&tile, G &&gen)
+{
+    if (scalar)
+        if (pa_status st = check_soa_scale(k.ssz, scalar, alpha)) return st;
+    auto shape = [&](auto s, auto m, auto dir) -> pa_status {
+        using S = typename decltype(s)::type;
+        if (k.kind == PA_KERNEL_SOA_GENERIC) return gen(s, m, dir);
+        if (k.kind != PA_KERNEL_SOA_LINEAR && k.kind != PA_KERNEL_SOA_TILE)
+            return fail("bad split/join kernel kind %d", k.kind);
+        return for_count<2>(k.n, [&](auto n) -> pa_status {
+            if (k.kind == PA_KERNEL_SOA_LINEAR)
+                return for_vec<16 / (int)sizeof(S)>(
+                    k.V, [&](auto v) { return lin(s, m, dir, n, v); });
+            constexpr int N = decltype(n)::value;
+            constexpr bool split = decltype(dir)::value == PA_SOA_SPLIT;
+            const int64_t row = split ? (int64_t)k.ti * N : k.ti;
+            if (k.ta < 1 || k.ti < 1 || k.tj != PA_SOA_TILE_TJ ||
+                k.pitch < row || (!split && k.plane < k.tj * k.pitch))
+                return fail("bad split/join tile selection");
+            const size_t lds = sizeof(S) * (split ? (size_t)k.tj * k.pitch
+                                                  : (size_t)N * k.plane);
+            if (lds > (64u << 10))
+                return fail("split/join tile needs %zu B of LDS", lds);
+            return tile(s, m, dir, n, lds);
+        });
+    };
+    auto policy = [&](auto s, auto m) -> pa_status {
+        return k.dir == PA_SOA_SPLIT ? shape(s, m, Int<PA_SOA_SPLIT>{})
+                                     : shape(s, m, Int<PA_SOA_JOIN>{});
+    };
+    const SoaNoMul none;
+    const SoaMul<float> mf{(float)alpha};
+    const SoaMul<double> md{alpha};
+    switch (k.ssz) {
+    case 4:
+        return scalar ? policy(Tag<uint32_t>{}, mf)
+                      : policy(Tag<uint32_t>{}, none);
+    case 8:
+        return scalar == PA_SCALAR_F32   ? policy(Tag<uint64_t>{}, mf)
+               : scalar == PA_SCALAR_F64 ? policy(Tag<uint64_t>{}, md)
+                                         : policy(Tag<uint64_t>{}, none);
+    case 16:
+        return scalar ? policy(Tag<uint4>{}, md) : policy(Tag<uint4>{}, none);
+    default:
+        return fail("bad scalar size %d", k.ssz);
+    }
+}
+
 /* aos is the source of a split and the destination of a join; scalar is the
  * PA_SCALAR_* code of a scaling launch by alpha, or 0 for a plain one */
 static pa_status launch_soa_sel(const SoaSel &k, void *aos,
@@ -2823,32 +2747,40 @@ static pa_status launch_soa_sel(const SoaSel &k, void *aos,
                                 hipStream_t stream)
 {
     if (k.kind == PA_KERNEL_NONE) return 0;
-    if (k.kind != PA_KERNEL_SOA_LINEAR && k.kind != PA_KERNEL_SOA_TILE &&
-        k.kind != PA_KERNEL_SOA_GENERIC)
-        return fail("bad split/join kernel kind %d", k.kind);
-    if (scalar)
-        if (pa_status st = check_soa_scale(k.ssz, scalar, alpha)) return st;
-    pa_status st;
-    const SoaNoMul none;
-    const SoaMul<float> mf{(float)alpha};
-    const SoaMul<double> md{alpha};
-#define SOA_DIR(S, M, m)                                                     \
-    (k.dir == PA_SOA_SPLIT                                                   \
-         ? launch_soa_t<S, M, PA_SOA_SPLIT>(k, aos, fields, m, stream)       \
-         : launch_soa_t<S, M, PA_SOA_JOIN>(k, aos, fields, m, stream))
-    if (k.ssz == 4)
-        st = scalar ? SOA_DIR(uint32_t, SoaMul<float>, mf)
-                    : SOA_DIR(uint32_t, SoaNoMul, none);
-    else if (k.ssz == 8)
-        st = scalar == PA_SCALAR_F32   ? SOA_DIR(uint64_t, SoaMul<float>, mf)
-             : scalar == PA_SCALAR_F64 ? SOA_DIR(uint64_t, SoaMul<double>, md)
-                                       : SOA_DIR(uint64_t, SoaNoMul, none);
-    else if (k.ssz == 16)
-        st = scalar ? SOA_DIR(uint4, SoaMul<double>, md)
-                    : SOA_DIR(uint4, SoaNoMul, none);
-    else
-        return fail("bad scalar size %d", k.ssz);
-#undef SOA_DIR
+    const Grid g = soa_grid(k);
+    const DescDev dd = to_dev(k.d);
+    dim3 grid;
+    if (k.kind != PA_KERNEL_SOA_GENERIC)
+        if (pa_status gst = grid2d(g.nblocks, 256, &grid)) return gst;
+    pa_status st = for_soa(
+        k, scalar, alpha,
+        [&](auto s, auto m, auto dir, auto n, auto v) {
+            using S = typename decltype(s)::type;
+            return launch(k_soa_linear<S, dir, n, v, decltype(m)>, grid,
+                          dim3(256), 0, stream, aos,
+                          soa_ptrs<n>(m, fields, n), dd);
+        },
+        [&](auto s, auto m, auto dir, auto n, size_t lds) {
+            using S = typename decltype(s)::type;
+            return launch(k_soa_tile<S, dir, n, decltype(m)>, grid,
+                          dim3(64, 4), lds, stream, aos,
+                          soa_ptrs<n>(m, fields, n), dd, k.ta, k.ti, k.pitch,
+                          k.plane, g.nti, g.njc, g.nblocks);
+        },
+        [&](auto s, auto m, auto dir) {
+            /* grid-stride kernel, at most PA_SOA_GENERIC_PTRS fields a
+             * launch, the component on blockIdx.z */
+            using S = typename decltype(s)::type;
+            const int gx = soa_generic_gx(k);
+            for (int c0 = 0; c0 < k.n; c0 += PA_SOA_GENERIC_PTRS) {
+                const int nc = std::min(k.n - c0, PA_SOA_GENERIC_PTRS);
+                launch(k_soa_generic<S, dir, decltype(m)>, dim3(gx, 1, nc),
+                       dim3(256), 0, stream, aos,
+                       soa_ptrs<PA_SOA_GENERIC_PTRS>(m, fields + c0, nc), dd,
+                       k.n, c0);
+            }
+            return (pa_status)0;
+        });
     if (st) return st;
     HIP_CHECK(hipGetLastError());
     return 0;
@@ -4454,30 +4386,43 @@ enum {
     STAGE_UNPACK = PA_STAGE_UNPACK
 };
 
+/* the kernel family of a stage entry: which selection of the item runs */
+enum Family { FAM_COPY, FAM_CVT, FAM_SCALE, FAM_SOA, FAM_FILL };
+
 struct StageItem {
-    KernelSel k;
-    bool cvt = false; /* wire plan, or a scaled plan's destination side: the
-                       * converting / scaling selection c runs, not k */
-    CvtSel c;
-    bool fill = false; /* keep plan: a zero-fill entry, fs instead of k */
-    FillSel fs;
-    /* a split / join stage (build_stage_soa): the selection s runs, on the
-     * vector-valued array and the field pointers (or staging slots) */
-    SoaSel s;
+    Family fam = FAM_COPY;
+    KernelSel k; /* FAM_COPY */
+    CvtSel c;    /* FAM_CVT (wire plan), FAM_SCALE (a scaled plan's
+                  * destination side) */
+    SoaSel s;    /* FAM_SOA: on the vector-valued array aos and the field
+                  * pointers (or staging slots) */
+    FillSel fs;  /* FAM_FILL (keep plan) */
     void *aos = nullptr;
     std::vector<void *> fields;
-    const void *src;
-    void *dst;
-    int64_t nti = 0, njc = 0, nblocks = 0;
+    const void *src = nullptr;
+    void *dst = nullptr;
+    Grid g;
+};
+
+/* What the entries of one grouped launch have in common, compared whole; a
+ * family sets the fields it does not use to 0. */
+struct StageSig {
+    int kind = 0;
+    int word = 0; /* copy kinds: bytes per word */
+    int op = 0;   /* converting kinds: wire op */
+    int vec = 0;  /* linear converting, scaling and split / join kinds: V */
+    bool operator==(const StageSig &o) const
+    {
+        return kind == o.kind && word == o.word && op == o.op && vec == o.vec;
+    }
 };
 
 struct StageLaunch {
-    int kind = 0, word = 0;
-    int op = 0, vec = 0; /* grouped converting kinds: wire op, V (linear) */
+    StageSig sig;
     bool grouped = false;
     std::vector<int> items;
     int64_t nblocks = 0;
-    void *d_mem = nullptr; /* grouped: first[nent] then GEntry[nent] */
+    void *d_mem = nullptr; /* grouped: first[nent] then the entries */
 };
 
 struct StageTable {
@@ -4489,63 +4434,72 @@ struct StageTable {
 
 #define PA_STAGE_TABLES_MAX 12
 
-/* workgroups of one selection, and the tile counts the tile kernels take:
- * the grid launch_sel() launches for it */
-static void sel_grid(const KernelSel &k, StageItem *it)
+/* Append an entry: a groupable one joins the open grouped launch of its
+ * signature, else it opens a new row, so rows stand in first-appearance
+ * order.  An entry without workgroups is dropped. */
+static void stage_push(StageTable *t, const StageItem &it,
+                       const StageSig &sig, bool groupable)
 {
-    const CopyDescH &w = k.d;
-    it->nti = it->njc = 0;
-    int ti = 0, tj = 0;
-    switch (k.kind) {
-    case PA_KERNEL_NONE:
-        it->nblocks = 0;
-        return;
-    case PA_KERNEL_COPY_1D:
-    case PA_KERNEL_COPY_1D_NT:
-    case PA_KERNEL_LINEAR:
-        it->nblocks = grid_exact(w.total, 256);
-        return;
-    case PA_KERNEL_GENERIC:
-        it->nblocks = grid_for(w.total, 256);
-        return;
-    case PA_KERNEL_TILE:
-        ti = k.word == 16 ? 32 : 128;
-        tj = k.word == 16 ? 32 : 64;
-        break;
-    case PA_KERNEL_TILE_VS:
-        ti = 64;
-        tj = 128;
-        break;
-    case PA_KERNEL_TILE_PK:
-        ti = tj = 128;
-        break;
-    default: /* PA_KERNEL_TILE_WIDE */
-        ti = k.ti;
-        tj = k.tj;
-        break;
-    }
-    int64_t nbatch = 1;
-    for (int a = 1; a < w.nd; a++)
-        if (a != k.ta) nbatch *= w.dims[a];
-    const int64_t ntj = (w.dims[k.ta] + tj - 1) / tj;
-    it->nti = (w.dims[0] + ti - 1) / ti;
-    it->njc = (ntj + k.sweep - 1) / k.sweep;
-    it->nblocks = it->nti * it->njc * nbatch;
+    if (it.g.nblocks == 0) return;
+    const int idx = (int)t->items.size();
+    t->items.push_back(it);
+    if (groupable)
+        for (auto &l : t->launches)
+            if (l.grouped && l.sig == sig) {
+                l.items.push_back(idx);
+                l.nblocks += it.g.nblocks;
+                return;
+            }
+    StageLaunch l;
+    l.sig = sig;
+    l.grouped = groupable;
+    l.items.push_back(idx);
+    l.nblocks = it.g.nblocks;
+    t->launches.push_back(l);
 }
 
-/* kinds with a grouped kernel; everything else launches per entry */
-static bool sel_groupable(const KernelSel &k, int *sig_kind)
+/* one copy entry: the grouped kernels cover the linear kinds and the
+ * one-tile-per-workgroup tiles, per word; everything else launches alone */
+static pa_status stage_add_copy(StageTable *t, const CopyDescH &d,
+                                int64_t ssz, int64_t ncomp, const void *src,
+                                void *dst)
 {
+    StageItem it;
+    it.src = src;
+    it.dst = dst;
+    if (pa_status st = select_kernel_comp(d, ssz, ncomp, src, dst, &it.k))
+        return st;
+    const KernelSel &k = it.k;
+    it.g = sel_grid(k);
+    StageSig sig;
+    sig.kind = k.kind;
+    sig.word = k.word;
+    bool grp = false;
     if (k.kind == PA_KERNEL_COPY_1D || k.kind == PA_KERNEL_LINEAR) {
-        *sig_kind = PA_KERNEL_LINEAR;
-        return true;
-    }
-    if ((k.kind == PA_KERNEL_TILE || k.kind == PA_KERNEL_TILE_VS) &&
-        k.sweep == 1) {
-        *sig_kind = k.kind;
-        return true;
-    }
-    return false;
+        sig.kind = PA_KERNEL_LINEAR;
+        grp = true;
+    } else if (k.kind == PA_KERNEL_TILE || k.kind == PA_KERNEL_TILE_VS)
+        grp = k.sweep == 1;
+    stage_push(t, it, sig, grp);
+    return 0;
+}
+
+/* one converting (fam FAM_CVT) or scaling (FAM_SCALE) entry, its selection
+ * already in it->c: linear entries of one (op, V) and tile entries of one op
+ * may share a grouped launch */
+static void stage_add_cvt(StageTable *t, StageItem *it, bool grouped)
+{
+    const CvtSel &c = it->c;
+    it->g.nblocks = cvt_grid(c, &it->g.nti, &it->g.njc);
+    const bool lin = c.kind == PA_KERNEL_CVT_LINEAR ||
+                     c.kind == PA_KERNEL_SCALE_LINEAR;
+    const bool tile = c.kind == PA_KERNEL_CVT_TILE ||
+                      c.kind == PA_KERNEL_SCALE_TILE;
+    StageSig sig;
+    sig.kind = c.kind;
+    sig.op = c.op;
+    sig.vec = lin ? c.V : 0;
+    stage_push(t, *it, sig, grouped && (lin || tile));
 }
 
 /* one zero-fill entry of a window of esz-byte elements; all of a stage share
@@ -4554,33 +4508,21 @@ static pa_status stage_add_fill(StageTable *t, const FillDescH &d,
                                 int64_t esz, void *dst)
 {
     StageItem it;
-    it.src = nullptr;
+    it.fam = FAM_FILL;
     it.dst = dst;
-    it.fill = true;
     if (pa_status st = select_fill(d, esz, dst, &it.fs)) return st;
-    it.nblocks = it.fs.nblocks;
-    if (it.nblocks == 0) return 0;
-    const int idx = (int)t->items.size();
-    t->items.push_back(it);
-    for (auto &l : t->launches)
-        if (l.grouped && l.kind == PA_KERNEL_FILL) {
-            l.items.push_back(idx);
-            l.nblocks += it.nblocks;
-            return 0;
-        }
-    StageLaunch l;
-    l.kind = PA_KERNEL_FILL;
-    l.word = 0;
-    l.grouped = true;
-    l.items.push_back(idx);
-    l.nblocks = it.nblocks;
-    t->launches.push_back(l);
+    it.g.nblocks = it.fs.nblocks;
+    StageSig sig;
+    sig.kind = PA_KERNEL_FILL;
+    stage_push(t, it, sig, true);
     return 0;
 }
 
-/* The launch list of one stage: select_kernel_comp() per entry, entries of
- * one signature (kind, word) share a grouped launch.  Host-only; pointers
- * are used for alignment only. */
+/* The launch list of one n-field stage: one copy (stage_add_copy()),
+ * converting or scaling (stage_add_cvt()) entry per sub-block and field, then
+ * a keep plan's fill entries; groupable entries of one StageSig share a
+ * grouped launch (stage_push()).  Host-only; pointers are used for alignment
+ * only. */
 static pa_status build_stage(const pa_plan *p, int n, int stage,
                              const void *const *srcs, void *const *dsts,
                              const void *send_buf, void *recv_buf,
@@ -4588,81 +4530,31 @@ static pa_status build_stage(const pa_plan *p, int n, int stage,
 {
     auto add_desc = [&](const CopyDescH &d, int which, const void *src,
                         void *dst) -> pa_status {
-        StageItem it;
-        it.src = src;
-        it.dst = dst;
         /* a scaled plan multiplies on the destination side only: the local
          * copy, the self unpack and the unpacks; its packs stay ordinary */
         const bool scaled = p->scale && (which == 0 || which == 2 || which == 4);
-        if (p->wire || scaled) {
-            /* converting kernels: ungrouped rows, one launch per entry,
-             * unless the plan asks for grouped ones */
-            const int op = scaled       ? 0
-                           : which == 0 ? PA_WIRE_ROUND
+        if (!p->wire && !scaled)
+            return stage_add_copy(t, d, p->ssz, p->ncomp, src, dst);
+        StageItem it;
+        it.src = src;
+        it.dst = dst;
+        if (scaled) {
+            it.fam = FAM_SCALE;
+            if (pa_status st = select_kernel_scale(d, p->scale, p->nscal, src,
+                                                   dst, &it.c))
+                return st;
+        } else {
+            const int op = which == 0 ? PA_WIRE_ROUND
                            : (which == 1 || which == 3) ? PA_WIRE_NARROW
                                                         : PA_WIRE_WIDEN;
-            it.cvt = true;
-            if (pa_status st =
-                    scaled ? select_kernel_scale(d, p->scale, p->nscal, src,
-                                                 dst, &it.c)
-                           : select_kernel_cvt(d, p->wire, op, p->ncomp, src,
-                                               dst, &it.c))
+            it.fam = FAM_CVT;
+            if (pa_status st = select_kernel_cvt(d, p->wire, op, p->ncomp,
+                                                 src, dst, &it.c))
                 return st;
-            it.nblocks = cvt_grid(it.c, &it.nti, &it.njc);
-            if (it.nblocks == 0) return 0;
-            /* PA_PLAN_GROUP_CVT: linear entries of one (op, V) and tile
-             * entries of one op share a grouped launch; the scaling kernels
-             * are grouped the same way without a flag */
-            const bool lin = it.c.kind == PA_KERNEL_CVT_LINEAR ||
-                             it.c.kind == PA_KERNEL_SCALE_LINEAR;
-            const bool grp = (scaled || p->group_cvt) &&
-                             (lin || it.c.kind == PA_KERNEL_CVT_TILE ||
-                              it.c.kind == PA_KERNEL_SCALE_TILE);
-            const int vec = lin ? it.c.V : 0;
-            const int idx = (int)t->items.size();
-            t->items.push_back(it);
-            if (grp)
-                for (auto &l : t->launches)
-                    if (l.grouped && l.kind == it.c.kind && l.op == op &&
-                        l.vec == vec) {
-                        l.items.push_back(idx);
-                        l.nblocks += it.nblocks;
-                        return 0;
-                    }
-            StageLaunch l;
-            l.kind = it.c.kind;
-            l.word = 0;
-            l.op = op;
-            l.vec = vec;
-            l.grouped = grp;
-            l.items.push_back(idx);
-            l.nblocks = it.nblocks;
-            t->launches.push_back(l);
-            return 0;
         }
-        if (pa_status st =
-                select_kernel_comp(d, p->ssz, p->ncomp, src, dst, &it.k))
-            return st;
-        sel_grid(it.k, &it);
-        if (it.nblocks == 0) return 0; /* empty: contributes no blocks */
-        int sig = 0;
-        const bool grp = sel_groupable(it.k, &sig);
-        const int idx = (int)t->items.size();
-        t->items.push_back(it);
-        if (grp)
-            for (auto &l : t->launches)
-                if (l.grouped && l.kind == sig && l.word == it.k.word) {
-                    l.items.push_back(idx);
-                    l.nblocks += it.nblocks;
-                    return 0;
-                }
-        StageLaunch l;
-        l.kind = grp ? sig : it.k.kind;
-        l.word = it.k.word;
-        l.grouped = grp;
-        l.items.push_back(idx);
-        l.nblocks = it.nblocks;
-        t->launches.push_back(l);
+        /* the converting kernels are grouped where the plan asks for it
+         * (PA_PLAN_GROUP_CVT), the scaling kernels always */
+        stage_add_cvt(t, &it, scaled || p->group_cvt);
         return 0;
     };
     /* every sub-block of `which` (of peer k) for field f */
@@ -4720,39 +4612,42 @@ static void free_stage_tables(pa_plan *p)
     p->tables.clear();
 }
 
-/* write the device tables of the grouped launches: a fresh allocation and
- * one blocking copy each, never modified afterwards */
+/* the device table of one grouped launch, first[nent] then E[nent]: a fresh
+ * allocation and one blocking copy, never modified afterwards.  make(item)
+ * is the entry of an item. */
+template <typename E, typename Make>
+static pa_status upload_launch(const StageTable &t, StageLaunch *l, Make make)
+{
+    const size_t ne = l->items.size();
+    std::vector<char> host(ne * (sizeof(int64_t) + sizeof(E)));
+    int64_t *first = (int64_t *)host.data();
+    char *ent = host.data() + ne * sizeof(int64_t);
+    int64_t acc = 0;
+    for (size_t i = 0; i < ne; i++) {
+        const StageItem &it = t.items[l->items[i]];
+        first[i] = acc;
+        acc += it.g.nblocks;
+        const E e = make(it);
+        memcpy(ent + i * sizeof(E), &e, sizeof e);
+    }
+    HIP_CHECK(hipMalloc(&l->d_mem, host.size()));
+    HIP_CHECK(hipMemcpy(l->d_mem, host.data(), host.size(),
+                        hipMemcpyHostToDevice));
+    return 0;
+}
+
 static pa_status upload_stage(StageTable *t)
 {
     for (auto &l : t->launches) {
         if (!l.grouped) continue;
-        const size_t ne = l.items.size();
-        if (l.kind == PA_KERNEL_FILL) {
-            std::vector<char> fhost(ne * sizeof(int64_t) +
-                                    ne * sizeof(GFill));
-            int64_t *ffirst = (int64_t *)fhost.data();
-            char *fent = fhost.data() + ne * sizeof(int64_t);
-            int64_t facc = 0;
-            for (size_t i = 0; i < ne; i++) {
-                const StageItem &it = t->items[l.items[i]];
-                ffirst[i] = facc;
-                facc += it.nblocks;
-                memcpy(fent + i * sizeof(GFill), &it.fs.g, sizeof(GFill));
-            }
-            HIP_CHECK(hipMalloc(&l.d_mem, fhost.size()));
-            HIP_CHECK(hipMemcpy(l.d_mem, fhost.data(), fhost.size(),
-                                hipMemcpyHostToDevice));
-            continue;
-        }
-        if (l.kind == PA_KERNEL_SOA_LINEAR || l.kind == PA_KERNEL_SOA_TILE) {
-            std::vector<char> shost(ne * sizeof(int64_t) + ne * sizeof(GSoa));
-            int64_t *sfirst = (int64_t *)shost.data();
-            char *sent = shost.data() + ne * sizeof(int64_t);
-            int64_t sacc = 0;
-            for (size_t i = 0; i < ne; i++) {
-                const StageItem &it = t->items[l.items[i]];
-                sfirst[i] = sacc;
-                sacc += it.nblocks;
+        pa_status st;
+        switch (t->items[l.items[0]].fam) {
+        case FAM_FILL:
+            st = upload_launch<GFill>(
+                *t, &l, [](const StageItem &it) { return it.fs.g; });
+            break;
+        case FAM_SOA:
+            st = upload_launch<GSoa>(*t, &l, [](const StageItem &it) {
                 GSoa g;
                 memset(&g, 0, sizeof g);
                 g.d = to_dev(it.s.d);
@@ -4763,205 +4658,151 @@ static pa_status upload_stage(StageTable *t)
                 g.ti = it.s.ti;
                 g.pitch = it.s.pitch;
                 g.plane = it.s.plane;
-                g.ntile_i = it.nti;
-                g.ntile_j = it.njc;
-                memcpy(sent + i * sizeof(GSoa), &g, sizeof g);
-            }
-            HIP_CHECK(hipMalloc(&l.d_mem, shost.size()));
-            HIP_CHECK(hipMemcpy(l.d_mem, shost.data(), shost.size(),
-                                hipMemcpyHostToDevice));
-            continue;
+                g.ntile_i = it.g.nti;
+                g.ntile_j = it.g.njc;
+                return g;
+            });
+            break;
+        default:
+            st = upload_launch<GEntry>(*t, &l, [](const StageItem &it) {
+                const bool copy = it.fam == FAM_COPY;
+                GEntry g;
+                memset(&g, 0, sizeof g);
+                g.d = to_dev(copy ? it.k.d : it.c.d);
+                g.src = it.src;
+                g.dst = it.dst;
+                g.ta = copy ? it.k.ta : it.c.ta;
+                g.ntile_i = it.g.nti;
+                g.njchunk = it.g.njc;
+                return g;
+            });
         }
-        std::vector<char> host(ne * sizeof(int64_t) + ne * sizeof(GEntry));
-        int64_t *first = (int64_t *)host.data();
-        GEntry *ent = (GEntry *)(host.data() + ne * sizeof(int64_t));
-        int64_t acc = 0;
-        for (size_t i = 0; i < ne; i++) {
-            const StageItem &it = t->items[l.items[i]];
-            first[i] = acc;
-            acc += it.nblocks;
-            GEntry g;
-            memset(&g, 0, sizeof g);
-            g.d = to_dev(it.cvt ? it.c.d : it.k.d);
-            g.src = it.src;
-            g.dst = it.dst;
-            g.ta = it.cvt ? it.c.ta : it.k.ta;
-            g.ntile_i = it.nti;
-            g.njchunk = it.njc;
-            memcpy(&ent[i], &g, sizeof g);
-        }
-        HIP_CHECK(hipMalloc(&l.d_mem, host.size()));
-        HIP_CHECK(hipMemcpy(l.d_mem, host.data(), host.size(),
-                            hipMemcpyHostToDevice));
+        if (st) return st;
     }
     return 0;
 }
 
-/* the grouped converting launch of (W, O): V resp. the component count pick
- * the instance, as in launch_cvt_linear() and launch_cvt_sel() */
-template <int W, int O>
-static void launch_group_cvt(const StageLaunch &l, int ncomp, dim3 grid,
-                             hipStream_t stream, const int64_t *first,
-                             const GEntry *ent, int ne)
-{
-#define GROUP_CVT(kern, block)                                               \
-    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
-                       l.nblocks)
-    if (l.kind == PA_KERNEL_CVT_LINEAR) {
-        if constexpr (W != PA_WIRE_F64_F32) {
-            if (l.vec == 4) {
-                GROUP_CVT((k_group_cvt_linear<W, O, 4>), dim3(256));
-                return;
-            }
-        }
-        if (l.vec == 2)
-            GROUP_CVT((k_group_cvt_linear<W, O, 2>), dim3(256));
-        else
-            GROUP_CVT((k_group_cvt_linear<W, O, 1>), dim3(256));
-    } else if (ncomp == 1)
-        GROUP_CVT((k_group_cvt_tile<W, O, 1>), dim3(64, 16));
-    else if (ncomp == 2)
-        GROUP_CVT((k_group_cvt_tile<W, O, 2>), dim3(64, 16));
-    else if (ncomp == 3)
-        GROUP_CVT((k_group_cvt_tile<W, O, 3>), dim3(64, 16));
-    else
-        GROUP_CVT((k_group_cvt_tile<W, O, 4>), dim3(64, 16));
-#undef GROUP_CVT
-}
-
-/* the grouped scaling launch of scalar type S: V resp. the scalars per
- * element pick the instance, as in launch_scale_sel_t() */
-template <typename S>
-static pa_status launch_group_scale(const StageLaunch &l, int nscal,
-                                    dim3 grid, hipStream_t stream,
-                                    const int64_t *first, const GEntry *ent,
-                                    int ne, S a)
-{
-#define GROUP_SCALE(kern, block)                                             \
-    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
-                       l.nblocks, a)
-    if (l.kind == PA_KERNEL_SCALE_LINEAR) {
-        if (l.vec != 1 && l.vec != 2 && !(l.vec == 4 && sizeof(S) == 4))
-            return fail("bad grouped scaling launch");
-        if constexpr (sizeof(S) == 4) {
-            if (l.vec == 4)
-                GROUP_SCALE((k_group_scale_linear<S, 4>), dim3(256));
-        }
-        if (l.vec == 2)
-            GROUP_SCALE((k_group_scale_linear<S, 2>), dim3(256));
-        else if (l.vec == 1)
-            GROUP_SCALE((k_group_scale_linear<S, 1>), dim3(256));
-    } else if (nscal == 1)
-        GROUP_SCALE((k_group_scale_tile<S, 1>), dim3(64, 16));
-    else if (nscal == 2)
-        GROUP_SCALE((k_group_scale_tile<S, 2>), dim3(64, 16));
-    else if (nscal == 3)
-        GROUP_SCALE((k_group_scale_tile<S, 3>), dim3(64, 16));
-    else if (nscal == 4)
-        GROUP_SCALE((k_group_scale_tile<S, 4>), dim3(64, 16));
-    else
-        return fail("bad grouped scaling launch");
-#undef GROUP_SCALE
-    return 0;
-}
-
-static pa_status launch_group(const pa_plan *p, const StageLaunch &l,
-                              hipStream_t stream)
+/* One grouped launch.  `it` is its first entry: everything that picks the
+ * kernel instance (the signature and, per family, the wire pair, the scalar
+ * type, the counts, the split / join tile shape) is the same for all of them.
+ * scalar and alpha as in launch_row(). */
+static pa_status launch_group(const StageLaunch &l, const StageItem &it,
+                              int scalar, double alpha, hipStream_t stream)
 {
     const int ne = (int)l.items.size();
     const int64_t *first = (const int64_t *)l.d_mem;
-    const GEntry *ent =
-        (const GEntry *)((const char *)l.d_mem + ne * sizeof(int64_t));
-    const int W = l.word;
+    const void *table = (const char *)l.d_mem + ne * sizeof(int64_t);
+    const GEntry *ent = (const GEntry *)table;
+    const int64_t nb = l.nblocks;
+    auto none = [](auto...) {
+        return fail("kernel kind without a grouped form");
+    };
     dim3 grid;
-    if (l.kind == PA_KERNEL_FILL) {
-        if (pa_status gst = grid2d(l.nblocks, 256, &grid)) return gst;
-        hipLaunchKernelGGL(k_group_fill, grid, dim3(256), 0, stream, first,
-                           (const GFill *)((const char *)l.d_mem +
-                                           ne * sizeof(int64_t)),
-                           ne, l.nblocks);
-        HIP_CHECK(hipGetLastError());
-        return 0;
+    pa_status st;
+    switch (it.fam) {
+    case FAM_FILL:
+        if (pa_status gst = grid2d(nb, 256, &grid)) return gst;
+        st = launch(k_group_fill, grid, dim3(256), 0, stream, first,
+                    (const GFill *)table, ne, nb);
+        break;
+    case FAM_CVT:
+        if (pa_status gst = cvt_dim(it.c.kind, nb, &grid)) return gst;
+        st = for_cvt(
+            it.c,
+            [&](auto w, auto o, auto v) {
+                return launch(k_group_cvt_linear<w, o, v>, grid, dim3(256), 0,
+                              stream, first, ent, ne, nb);
+            },
+            [&](auto w, auto o, auto nc) {
+                return launch(k_group_cvt_tile<w, o, nc>, grid, dim3(64, 16),
+                              0, stream, first, ent, ne, nb);
+            },
+            none);
+        break;
+    case FAM_SCALE:
+        if (pa_status gst = cvt_dim(it.c.kind, nb, &grid)) return gst;
+        st = for_scale(
+            it.c, alpha,
+            [&](auto a, auto v) {
+                return launch(k_group_scale_linear<decltype(a), v>, grid,
+                              dim3(256), 0, stream, first, ent, ne, nb, a);
+            },
+            [&](auto a, auto nc) {
+                return launch(k_group_scale_tile<decltype(a), nc>, grid,
+                              dim3(64, 16), 0, stream, first, ent, ne, nb, a);
+            },
+            none);
+        break;
+    case FAM_SOA:
+        if (pa_status gst = grid2d(nb, 256, &grid)) return gst;
+        st = for_soa(
+            it.s, scalar, alpha,
+            [&](auto s, auto m, auto dir, auto n, auto v) {
+                using S = typename decltype(s)::type;
+                return launch(k_group_soa_linear<S, dir, n, v, decltype(m)>,
+                              grid, dim3(256), 0, stream, first,
+                              (const GSoa *)table, ne, nb, m);
+            },
+            [&](auto s, auto m, auto dir, auto n, size_t lds) {
+                using S = typename decltype(s)::type;
+                return launch(k_group_soa_tile<S, dir, n, decltype(m)>, grid,
+                              dim3(64, 4), lds, stream, first,
+                              (const GSoa *)table, ne, nb, m);
+            },
+            none);
+        break;
+    default: /* FAM_COPY: the signature holds the grouped kind and the word */
+        st = for_word(l.sig.word, [&](auto tag) -> pa_status {
+            using T = typename decltype(tag)::type;
+            constexpr bool wide = sizeof(T) == 16;
+            constexpr int NR = wide ? 8 : 16;
+            switch (l.sig.kind) {
+            case PA_KERNEL_LINEAR:
+                if (pa_status gst = grid2d(nb, 256, &grid)) return gst;
+                return launch(k_group_linear<T>, grid, dim3(256), 0, stream,
+                              first, ent, ne, nb);
+            case PA_KERNEL_TILE_VS:
+                if constexpr (sizeof(T) == 8) {
+                    if (pa_status gst = grid2d(nb, 64 * 16, &grid)) return gst;
+                    return launch(k_group_tile_vs<T, 64, 128, 16>, grid,
+                                  dim3(64, 16), 0, stream, first, ent, ne, nb);
+                }
+                break;
+            case PA_KERNEL_TILE:
+                if (pa_status gst = grid2d(nb, 64 * NR, &grid)) return gst;
+                return launch(
+                    k_group_tile<T, wide ? 32 : 128, wide ? 32 : 64, NR>,
+                    grid, dim3(64, NR), 0, stream, first, ent, ne, nb);
+            }
+            return fail("bad grouped kind %d", l.sig.kind);
+        });
     }
-    if (l.kind == PA_KERNEL_CVT_LINEAR || l.kind == PA_KERNEL_CVT_TILE) {
-        const bool lin = l.kind == PA_KERNEL_CVT_LINEAR;
-        if (lin ? (l.vec != 1 && l.vec != 2 &&
-                   !(l.vec == 4 && p->wire != PA_WIRE_F64_F32))
-                : (p->ncomp < 1 || p->ncomp > PA_CVT_TILE_MAX_COMP))
-            return fail("bad grouped converting launch");
-        if (pa_status gst = grid2d(l.nblocks, lin ? 256 : 64 * 16, &grid))
-            return gst;
-#define GROUP_CVT_WO(W, O)                                                   \
-    launch_group_cvt<W, O>(l, (int)p->ncomp, grid, stream, first, ent, ne)
-        CVT_FOR_WIRE_OP(p->wire, l.op, GROUP_CVT_WO)
-#undef GROUP_CVT_WO
-        HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (l.kind == PA_KERNEL_SCALE_LINEAR || l.kind == PA_KERNEL_SCALE_TILE) {
-        const bool lin = l.kind == PA_KERNEL_SCALE_LINEAR;
-        if (pa_status gst = grid2d(l.nblocks, lin ? 256 : 64 * 16, &grid))
-            return gst;
-        pa_status st;
-        if (p->scale == PA_SCALAR_F32)
-            st = launch_group_scale<float>(l, (int)p->nscal, grid, stream,
-                                           first, ent, ne, (float)p->alpha);
-        else if (p->scale == PA_SCALAR_F64)
-            st = launch_group_scale<double>(l, (int)p->nscal, grid, stream,
-                                            first, ent, ne, p->alpha);
-        else
-            st = fail("grouped scaling launch on a plan without a scale");
-        if (st) return st;
-        HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-#define GROUP_GRID(threads)                                                  \
-    do {                                                                     \
-        if (pa_status gst = grid2d(l.nblocks, threads, &grid)) return gst;   \
-    } while (0)
-#define GROUP_LAUNCH(kern, block)                                            \
-    hipLaunchKernelGGL(kern, grid, block, 0, stream, first, ent, ne,         \
-                       l.nblocks)
-    if (l.kind == PA_KERNEL_LINEAR) {
-        GROUP_GRID(256);
-        if (W == 16)
-            GROUP_LAUNCH(k_group_linear<uint4>, dim3(256));
-        else if (W == 8)
-            GROUP_LAUNCH(k_group_linear<uint64_t>, dim3(256));
-        else if (W == 4)
-            GROUP_LAUNCH(k_group_linear<uint32_t>, dim3(256));
-        else if (W == 2)
-            GROUP_LAUNCH(k_group_linear<uint16_t>, dim3(256));
-        else
-            GROUP_LAUNCH(k_group_linear<uint8_t>, dim3(256));
-    } else if (l.kind == PA_KERNEL_TILE_VS) {
-        GROUP_GRID(64 * 16);
-        GROUP_LAUNCH((k_group_tile_vs<uint64_t, 64, 128, 16>), dim3(64, 16));
-    } else if (l.kind == PA_KERNEL_TILE) {
-        if (W == 16) {
-            GROUP_GRID(64 * 8);
-            GROUP_LAUNCH((k_group_tile<uint4, 32, 32, 8>), dim3(64, 8));
-        } else {
-            GROUP_GRID(64 * 16);
-            if (W == 8)
-                GROUP_LAUNCH((k_group_tile<uint64_t, 128, 64, 16>),
-                             dim3(64, 16));
-            else if (W == 4)
-                GROUP_LAUNCH((k_group_tile<uint32_t, 128, 64, 16>),
-                             dim3(64, 16));
-            else if (W == 2)
-                GROUP_LAUNCH((k_group_tile<uint16_t, 128, 64, 16>),
-                             dim3(64, 16));
-            else
-                GROUP_LAUNCH((k_group_tile<uint8_t, 128, 64, 16>),
-                             dim3(64, 16));
-        }
-    } else
-        return fail("bad grouped kind %d", l.kind);
-#undef GROUP_GRID
-#undef GROUP_LAUNCH
+    if (st) return st;
     HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+/* One row of a stage table, grouped or single, by its family.  alpha
+ * multiplies in the scaling kernels; scalar is the PA_SCALAR_* code of a
+ * scaling split / join call, 0 for a plain one. */
+static pa_status launch_row(const StageTable &t, const StageLaunch &l,
+                            int scalar, double alpha, hipStream_t stream)
+{
+    const StageItem &it = t.items[l.items[0]];
+    if (l.grouped) return launch_group(l, it, scalar, alpha, stream);
+    switch (it.fam) {
+    case FAM_COPY:
+        return launch_sel(it.k, it.src, it.dst, stream);
+    case FAM_CVT:
+        return launch_cvt_sel(it.c, it.src, it.dst, stream);
+    case FAM_SCALE:
+        return launch_scale_sel(it.c, it.src, it.dst, alpha, stream);
+    case FAM_SOA:
+        return launch_soa_sel(it.s, it.aos, it.fields.data(), scalar, alpha,
+                              stream);
+    default:
+        return fail("a fill entry outside a grouped launch");
+    }
 }
 
 static void stage_key(const pa_plan *p, int n, int stage,
@@ -5034,23 +4875,62 @@ static pa_status exchange_many(pa_plan *p, int n, hipStream_t stream)
     return 0;
 }
 
-/* the plan's LRU cache of stage tables: the table of `key`, or null; and room
- * for one more, by dropping the least recently used at capacity */
-static StageTable *table_find(pa_plan *p, const std::vector<uintptr_t> &key)
+/* The second word of a table key says which stage the table is of: the
+ * n-field stages carry their STAGE_* code (stage_key()), the split / join
+ * stages STAGE_CODE_SOA + 4 * direction + stage, past all of those. */
+enum { STAGE_CODE_SOA = 16 };
+
+/* The plan's LRU cache of stage tables: the table of `key`, built by
+ * build(table) and uploaded on a miss, after dropping the least recently
+ * used one at capacity. */
+template <typename Build>
+static pa_status stage_table_get(pa_plan *p, const std::vector<uintptr_t> &key,
+                                 StageTable **out, Build build)
 {
+    StageTable *t = nullptr;
     for (auto *c : p->tables)
-        if (c->key == key) return c;
-    return nullptr;
+        if (c->key == key) { t = c; break; }
+    if (!t) {
+        if ((int)p->tables.size() >= PA_STAGE_TABLES_MAX) {
+            size_t old = 0;
+            for (size_t i = 1; i < p->tables.size(); i++)
+                if (p->tables[i]->stamp < p->tables[old]->stamp) old = i;
+            free_table(p->tables[old]);
+            p->tables.erase(p->tables.begin() + old);
+        }
+        t = new StageTable;
+        t->key = key;
+        pa_status st = build(t);
+        if (!st) st = upload_stage(t);
+        if (st) { free_table(t); return st; }
+        p->tables.push_back(t);
+        p->table_builds++;
+    }
+    t->stamp = ++p->table_clock;
+    *out = t;
+    return 0;
 }
 
-static void table_make_room(pa_plan *p)
+/* the (kind, grouped, entries, workgroups) rows the stage queries report */
+static void table_rows(const StageTable &t, int max_rows, int64_t (*rows)[4],
+                       int *nrows)
 {
-    if ((int)p->tables.size() < PA_STAGE_TABLES_MAX) return;
-    size_t old = 0;
-    for (size_t i = 1; i < p->tables.size(); i++)
-        if (p->tables[i]->stamp < p->tables[old]->stamp) old = i;
-    free_table(p->tables[old]);
-    p->tables.erase(p->tables.begin() + old);
+    *nrows = (int)t.launches.size();
+    for (int i = 0; i < *nrows && i < max_rows; i++) {
+        const StageLaunch &l = t.launches[i];
+        rows[i][0] = l.sig.kind;
+        rows[i][1] = l.grouped ? 1 : 0;
+        rows[i][2] = (int64_t)l.items.size();
+        rows[i][3] = l.nblocks;
+    }
+}
+
+static pa_status run_table(const StageTable &t, int scalar, double alpha,
+                           hipStream_t stream)
+{
+    for (auto &l : t.launches)
+        if (pa_status st = launch_row(t, l, scalar, alpha, stream)) return st;
+    return 0;
 }
 
 static pa_status run_stage(pa_plan *p, int n, int stage,
@@ -5060,33 +4940,13 @@ static pa_status run_stage(pa_plan *p, int n, int stage,
     if (pa_status st = many_check(p, n, stage, srcs, dsts)) return st;
     std::vector<uintptr_t> key;
     stage_key(p, n, stage, srcs, dsts, &key);
-    StageTable *t = table_find(p, key);
-    if (!t) {
-        table_make_room(p);
-        t = new StageTable;
-        t->key = key;
-        pa_status st = build_stage(p, n, stage, srcs, dsts, p->send_buf,
-                                   p->recv_buf, t);
-        if (!st) st = upload_stage(t);
-        if (st) { free_table(t); return st; }
-        p->tables.push_back(t);
-        p->table_builds++;
-    }
-    t->stamp = ++p->table_clock;
-    for (auto &l : t->launches) {
-        pa_status st;
-        if (l.grouped)
-            st = launch_group(p, l, stream);
-        else {
-            const StageItem &it = t->items[l.items[0]];
-            st = !it.cvt ? launch_sel(it.k, it.src, it.dst, stream)
-                 : it.c.scalar
-                     ? launch_scale_sel(it.c, it.src, it.dst, p->alpha, stream)
-                     : launch_cvt_sel(it.c, it.src, it.dst, stream);
-        }
-        if (st) return st;
-    }
-    return 0;
+    StageTable *t;
+    if (pa_status st = stage_table_get(p, key, &t, [&](StageTable *nt) {
+            return build_stage(p, n, stage, srcs, dsts, p->send_buf,
+                               p->recv_buf, nt);
+        }))
+        return st;
+    return run_table(*t, 0, p->alpha, stream);
 }
 
 extern "C" {
@@ -5154,14 +5014,7 @@ pa_status pa_plan_stage_launches(const pa_plan *p, int n, int stage,
     if (pa_status st =
             build_stage(p, n, stage, s.data(), d.data(), send, recv, &t))
         return st;
-    *nrows = (int)t.launches.size();
-    for (int i = 0; i < *nrows && i < max_rows; i++) {
-        const StageLaunch &l = t.launches[i];
-        rows[i][0] = l.kind;
-        rows[i][1] = l.grouped ? 1 : 0;
-        rows[i][2] = (int64_t)l.items.size();
-        rows[i][3] = l.nblocks;
-    }
+    table_rows(t, max_rows, rows, nrows);
     return 0;
 }
 
@@ -5425,44 +5278,17 @@ static pa_status build_stage_soa(const pa_plan *p, int n, int dir, int stage,
 {
     auto add_desc = [&](const CopyDescH &d, void *const *fp) -> pa_status {
         StageItem it;
-        it.src = nullptr;
-        it.dst = nullptr;
+        it.fam = FAM_SOA;
         it.aos = aos;
         it.fields.assign(fp, fp + n);
         if (pa_status st = select_kernel_soa(d, p->ssz, n, dir, aos, fp, &it.s))
             return st;
         const SoaSel &k = it.s;
-        if (k.kind == PA_KERNEL_NONE) return 0; /* empty: no blocks */
-        if (k.kind == PA_KERNEL_SOA_LINEAR)
-            it.nblocks = grid_exact(k.d.total, 256);
-        else if (k.kind == PA_KERNEL_SOA_GENERIC)
-            it.nblocks = (int64_t)grid_for(k.d.total, 256) * n;
-        else {
-            int64_t nbatch = 1;
-            for (int a = 1; a < k.d.nd; a++)
-                if (a != k.ta) nbatch *= k.d.dims[a];
-            it.nti = (k.d.dims[0] + k.ti - 1) / k.ti;
-            it.njc = (k.d.dims[k.ta] + k.tj - 1) / k.tj;
-            it.nblocks = it.nti * it.njc * nbatch;
-        }
-        const bool grp = grouped && k.kind != PA_KERNEL_SOA_GENERIC;
-        const int vec = k.kind == PA_KERNEL_SOA_LINEAR ? k.V : 0;
-        const int idx = (int)t->items.size();
-        t->items.push_back(it);
-        if (grp)
-            for (auto &l : t->launches)
-                if (l.grouped && l.kind == k.kind && l.vec == vec) {
-                    l.items.push_back(idx);
-                    l.nblocks += it.nblocks;
-                    return 0;
-                }
-        StageLaunch l;
-        l.kind = k.kind;
-        l.vec = vec;
-        l.grouped = grp;
-        l.items.push_back(idx);
-        l.nblocks = it.nblocks;
-        t->launches.push_back(l);
+        it.g = soa_grid(k);
+        StageSig sig;
+        sig.kind = k.kind;
+        sig.vec = k.kind == PA_KERNEL_SOA_LINEAR ? k.V : 0;
+        stage_push(t, it, sig, grouped && k.kind != PA_KERNEL_SOA_GENERIC);
         return 0;
     };
     /* one staged block with the vector-valued array on its other side:
@@ -5500,151 +5326,29 @@ static pa_status build_stage_soa(const pa_plan *p, int n, int dir, int stage,
     return 0;
 }
 
-/* the grouped launch of one S, multiplier policy, direction and N: V resp.
- * the tile picks the instance, as in launch_soa_n() */
-template <typename S, typename M, int DIR, int N>
-static pa_status launch_group_soa_n(const StageLaunch &l, const SoaSel &k,
-                                    const M &m, const int64_t *first,
-                                    const GSoa *ent, int ne,
-                                    hipStream_t stream)
-{
-    dim3 grid;
-    if (pa_status gst = grid2d(l.nblocks, 256, &grid)) return gst;
-    if (l.kind == PA_KERNEL_SOA_LINEAR) {
-        constexpr int VMAX = 16 / (int)sizeof(S);
-#define GROUP_SOA_LIN(VV)                                                    \
-    hipLaunchKernelGGL((k_group_soa_linear<S, DIR, N, VV, M>), grid,         \
-                       dim3(256), 0, stream, first, ent, ne, l.nblocks, m)
-        if (l.vec < 1 || l.vec > VMAX) return fail("bad vector width %d", l.vec);
-        if constexpr (VMAX >= 4) {
-            if (l.vec == 4) { GROUP_SOA_LIN(4); return 0; }
-        }
-        if constexpr (VMAX >= 2) {
-            if (l.vec == 2) { GROUP_SOA_LIN(2); return 0; }
-        }
-        if (l.vec != 1) return fail("bad vector width %d", l.vec);
-        GROUP_SOA_LIN(1);
-#undef GROUP_SOA_LIN
-        return 0;
-    }
-    /* PA_KERNEL_SOA_TILE: one tile shape for the stage, that of entry 0 */
-    const int64_t row = DIR == PA_SOA_SPLIT ? (int64_t)k.ti * N : k.ti;
-    if (k.ta < 1 || k.ti < 1 || k.tj != PA_SOA_TILE_TJ || k.pitch < row ||
-        (DIR == PA_SOA_JOIN && k.plane < k.tj * k.pitch))
-        return fail("bad split/join tile selection");
-    const size_t lds = sizeof(S) * (DIR == PA_SOA_SPLIT
-                                        ? (size_t)k.tj * k.pitch
-                                        : (size_t)N * k.plane);
-    if (lds > (64u << 10))
-        return fail("split/join tile needs %zu B of LDS", lds);
-    hipLaunchKernelGGL((k_group_soa_tile<S, DIR, N, M>), grid, dim3(64, 4),
-                       lds, stream, first, ent, ne, l.nblocks, m);
-    return 0;
-}
-
-template <typename S, typename M, int DIR>
-static pa_status launch_group_soa_t(const StageLaunch &l, const SoaSel &k,
-                                    const M &m, const int64_t *first,
-                                    const GSoa *ent, int ne,
-                                    hipStream_t stream)
-{
-    switch (k.n) {
-    case 2:
-        return launch_group_soa_n<S, M, DIR, 2>(l, k, m, first, ent, ne, stream);
-    case 3:
-        return launch_group_soa_n<S, M, DIR, 3>(l, k, m, first, ent, ne, stream);
-    case 4:
-        return launch_group_soa_n<S, M, DIR, 4>(l, k, m, first, ent, ne, stream);
-    default: return fail("bad grouped split/join launch: n = %d", k.n);
-    }
-}
-
-/* k is the selection of the launch's first entry: S, n, the direction and
- * (tile) the shape are the same for all of them; scalar and alpha as in
- * launch_soa_sel() */
-static pa_status launch_group_soa(const StageLaunch &l, const SoaSel &k,
-                                  int scalar, double alpha,
-                                  hipStream_t stream)
-{
-    const int ne = (int)l.items.size();
-    const int64_t *first = (const int64_t *)l.d_mem;
-    const GSoa *ent =
-        (const GSoa *)((const char *)l.d_mem + ne * sizeof(int64_t));
-    if (scalar)
-        if (pa_status st = check_soa_scale(k.ssz, scalar, alpha)) return st;
-    pa_status st;
-    const SoaNoMul none;
-    const SoaMul<float> mf{(float)alpha};
-    const SoaMul<double> md{alpha};
-#define GROUP_SOA_DIR(S, M, m)                                               \
-    (k.dir == PA_SOA_SPLIT                                                   \
-         ? launch_group_soa_t<S, M, PA_SOA_SPLIT>(l, k, m, first, ent, ne,   \
-                                                  stream)                    \
-         : launch_group_soa_t<S, M, PA_SOA_JOIN>(l, k, m, first, ent, ne,    \
-                                                 stream))
-    if (k.ssz == 4)
-        st = scalar ? GROUP_SOA_DIR(uint32_t, SoaMul<float>, mf)
-                    : GROUP_SOA_DIR(uint32_t, SoaNoMul, none);
-    else if (k.ssz == 8)
-        st = scalar == PA_SCALAR_F32
-                 ? GROUP_SOA_DIR(uint64_t, SoaMul<float>, mf)
-             : scalar == PA_SCALAR_F64
-                 ? GROUP_SOA_DIR(uint64_t, SoaMul<double>, md)
-                 : GROUP_SOA_DIR(uint64_t, SoaNoMul, none);
-    else if (k.ssz == 16)
-        st = scalar ? GROUP_SOA_DIR(uint4, SoaMul<double>, md)
-                    : GROUP_SOA_DIR(uint4, SoaNoMul, none);
-    else
-        return fail("bad scalar size %d", k.ssz);
-#undef GROUP_SOA_DIR
-    if (st) return st;
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 /* One split / join stage of a PA_PLAN_GROUP_SOA plan through its cached
- * table.  The key is (n, direction, stage, the vector-valued array, the field
- * pointers); neither the scale nor alpha is part of it, so a scaled call, a
- * plain one and one with another alpha share a table. */
+ * table.  The key is (n, direction and stage, the vector-valued array, the
+ * field pointers); neither the scale nor alpha is part of it, so a scaled
+ * call, a plain one and one with another alpha share a table. */
 static pa_status run_stage_soa(pa_plan *p, int n, int dir, int stage,
                                void *aos, void *const *fields, int scale,
                                double alpha, hipStream_t stream)
 {
     std::vector<uintptr_t> key;
     key.push_back((uintptr_t)n);
-    /* past every stage code of stage_key() */
-    key.push_back((uintptr_t)(16 + 4 * dir + stage));
+    key.push_back((uintptr_t)(STAGE_CODE_SOA + 4 * dir + stage));
     key.push_back((uintptr_t)p->send_buf);
     key.push_back((uintptr_t)p->recv_buf);
     key.push_back((uintptr_t)aos);
     for (int c = 0; c < n; c++)
         key.push_back(stage == STAGE_LOCAL ? (uintptr_t)fields[c] : 0);
-    StageTable *t = table_find(p, key);
-    if (!t) {
-        table_make_room(p);
-        t = new StageTable;
-        t->key = key;
-        pa_status st = build_stage_soa(p, n, dir, stage, aos, fields,
-                                       p->send_buf, p->recv_buf, true, t);
-        if (!st) st = upload_stage(t);
-        if (st) { free_table(t); return st; }
-        p->tables.push_back(t);
-        p->table_builds++;
-    }
-    t->stamp = ++p->table_clock;
-    for (auto &l : t->launches) {
-        const StageItem &it = t->items[l.items[0]];
-        pa_status st;
-        if (l.kind == PA_KERNEL_FILL)
-            st = launch_group(p, l, stream);
-        else if (l.grouped)
-            st = launch_group_soa(l, it.s, scale, alpha, stream);
-        else
-            st = launch_soa_sel(it.s, it.aos, it.fields.data(), scale, alpha,
-                                stream);
-        if (st) return st;
-    }
-    return 0;
+    StageTable *t;
+    if (pa_status st = stage_table_get(p, key, &t, [&](StageTable *nt) {
+            return build_stage_soa(p, n, dir, stage, aos, fields, p->send_buf,
+                                   p->recv_buf, true, nt);
+        }))
+        return st;
+    return run_table(*t, scale, alpha, stream);
 }
 
 /* The four stages behind the plain and the scaled calls, arguments already
@@ -5781,14 +5485,7 @@ pa_status pa_plan_stage_launches_soa(const pa_plan *p, int n, int dir,
                                        f.data(), send, recv,
                                        pa_plan_group_soa(p) != 0, &t))
         return st;
-    *nrows = (int)t.launches.size();
-    for (int i = 0; i < *nrows && i < max_rows; i++) {
-        const StageLaunch &l = t.launches[i];
-        rows[i][0] = l.kind;
-        rows[i][1] = l.grouped ? 1 : 0;
-        rows[i][2] = (int64_t)l.items.size();
-        rows[i][3] = l.nblocks;
-    }
+    table_rows(t, max_rows, rows, nrows);
     return 0;
 }
 

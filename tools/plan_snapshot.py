@@ -19,6 +19,10 @@ Only public queries are serialised.  On the Python side the ``*_subs``
 tables and ``stage_descs`` are public for keep plans only (an ordinary plan
 is read through ``pack`` / ``unpack`` / ``local`` / ``self_pack`` /
 ``self_unpack`` and ``copydesc_many``), so that is where they are recorded.
+
+``--stage`` selects a second matrix with a fixture of its own,
+``tests/golden/stage_snapshot.json``: the launch rows of the engine's stage
+tables for every plan flavour (see "the stage matrix" below).
 """
 
 from __future__ import annotations
@@ -104,8 +108,9 @@ def _try(fn):
 class Recorder:
     """``rec(query, key, value)`` appends one line to the query's stream."""
 
-    def __init__(self):
-        self.lines = {q: [] for q in QUERIES}
+    def __init__(self, queries=None):
+        self.queries = QUERIES if queries is None else queries
+        self.lines = {q: [] for q in self.queries}
 
     def __call__(self, query, key, value):
         self.lines[query].append(f"{key} -> {value!r}")
@@ -116,7 +121,7 @@ class Recorder:
     def digest(self):
         h = hashlib.sha256()
         loc = []
-        for q in QUERIES:
+        for q in self.queries:
             t = (q + "\n" + self.text(q) + "\n").encode()
             h.update(t)
             loc.append(hashlib.sha256(t).hexdigest()[:4])
@@ -288,33 +293,208 @@ def case_id(c):
     return f"{cfg}/{variant}" + ("/wire" if wire is not None else "")
 
 
-def first_difference(want, got):
+def first_difference(want, got, queries=QUERIES):
     """The first query whose locator differs between two ``[digest,
     locator]`` fixture entries, or None if only the digest does."""
-    for i, q in enumerate(QUERIES):
+    for i, q in enumerate(queries):
         if want[1][4 * i:4 * i + 4] != got[1][4 * i:4 * i + 4]:
             return q
     return None
 
 
+# ---- the stage matrix: launch rows of every plan flavour ------------------
+#
+# A second fixture, ``tests/golden/stage_snapshot.json``, pins what the
+# engine's stage tables decide: the rows of ``pa_plan_stage_launches`` and
+# ``pa_plan_stage_launches_soa``, the kernel-kind query of every entry behind
+# them, and the error texts, for every plan flavour, on aligned and on offset
+# pointers.  ``tests/test_stage_snapshot.py`` compares against it.
+#
+#     python tools/plan_snapshot.py --stage --write
+#     python tools/plan_snapshot.py --stage --dump CASE
+
+STAGE_FIXTURE = os.path.join(REPO, "tests", "golden", "stage_snapshot.json")
+STAGE_QUERIES = ("stage.meta", "stage.launches", "stage.kind",
+                 "soa.launches", "soa.kind")
+STAGE_CONFIGS = tuple(c for c in CONFIGS if c.startswith(("g1x1", "g2x3")))
+SOA_NS = (2, 3, 4, 5)
+
+# name: NativePlan arguments, then (scalar, alpha) of pa_plan_set_scale
+FLAVOURS = {
+    "plain": (dict(elem_size=8), None),
+    "comp": (dict(elem_size=4, ncomp=3), None),
+    "scale32": (dict(elem_size=4, ncomp=2), (native.SCALAR_F32, 0.5)),
+    "scale64": (dict(elem_size=8), (native.SCALAR_F64, 0.25)),
+    "keep": (dict(elem_size=8, keep="partial"), None),
+    "soa": (dict(elem_size=4), None),
+    "soa_group": (dict(elem_size=4, group_soa=True), None),
+    "soa_group8": (dict(elem_size=8, group_soa=True), None),
+    "keep_soa_group": (dict(elem_size=4, keep="partial", group_soa=True),
+                       None),
+    # a split or join takes its scale per call; a plan with one set answers
+    # the split / join queries with an error text
+    "soa_scaled": (dict(elem_size=4, group_soa=True),
+                   (native.SCALAR_F32, 0.5)),
+}
+for _w, _name, _sz in ((native.WIRE_F64_F32, "f64_f32", 8),
+                       (native.WIRE_F32_F16, "f32_f16", 4),
+                       (native.WIRE_F32_BF16, "f32_bf16", 4)):
+    for _nc in (1, 2):
+        for _g in (False, True):
+            FLAVOURS[f"wire_{_name}_nc{_nc}" + ("_group" if _g else "")] = (
+                dict(elem_size=_sz, ncomp=_nc, wire=_w, group_cvt=_g), None)
+
+# Stand-in pointers, never dereferenced.  name: byte offset of pointer i of a
+# list; "mixed" offsets field i by 4 * i bytes so the rows of a stage split.
+POINTERS = {"a256": lambda i: 0, "o4": lambda i: 4, "o8": lambda i: 8,
+            "mixed": lambda i: 4 * (i % 3)}
+SRC0, DST0, AOS0, SEND0, RECV0 = (1 << 24, 2 << 24, 3 << 24, 4 << 24, 5 << 24)
+
+
+def _stage_kind(nat, d, which, scale, src, dst):
+    if nat.wire is not None:
+        return _kind_ptr(d, which, nat.wire, nat.ncomp, src, dst)
+    if scale is not None and which in (0, 2, 4):
+        nscal = nat.elem_size * nat.ncomp // native.SCALAR_BYTES[scale[0]]
+        return tuple(native.copy_kernel_kind_scale(d, scale[0], nscal, src,
+                                                   dst))
+    return tuple(native.copy_kernel_kind(d, nat.elem_size, src, dst,
+                                         ncomp=nat.ncomp))
+
+
+def _kind_ptr(d, which, wire, ncomp, src, dst):
+    op = (native.WIRE_ROUND if which == 0 else
+          native.WIRE_NARROW if which in (1, 3) else native.WIRE_WIDEN)
+    return tuple(native.copy_kernel_kind_wire(d, wire, op, ncomp, src, dst))
+
+
+def _entry_descs(nat, n, f, which, k):
+    """The descriptors behind ``which`` of peer ``k`` for field ``f``."""
+    if nat.keep is not None:
+        return [nat.copydesc_sub(n, f, which, k, s)
+                for s in range(nat.nsub(which, k))]
+    d = nat.copydesc_many(n, f, which, k)
+    return [] if d is None else [d]
+
+
+def record_stage_plan(rec, tag, nat, scale, off):
+    npeer = nat.nproc_sub if nat.r_dim >= 0 else 0
+    send, recv = SEND0 + off(0), RECV0 + off(1)
+    nat.set_buffers(send, recv)
+    rec("stage.meta", tag, (nat.nproc_sub, nat.r_dim, nat.my_k,
+                            nat.plan_wire(), nat.plan_keep(),
+                            nat.plan_scale(), nat.group_cvt(),
+                            nat.group_soa()))
+    for n in (1, 3):
+        srcs = [SRC0 + (f << 20) + off(f) for f in range(n)]
+        dsts = [DST0 + (f << 20) + off(f + 1) for f in range(n)]
+        for stage in range(3):
+            rec("stage.launches", f"{tag} n={n} stage={stage}",
+                _try(lambda: [tuple(r) for r in nat.stage_launches(
+                    n, stage, srcs, dsts)]))
+        for f in range(n):
+            # (which, source, destination) as the stages pair them
+            sides = ((0, srcs[f], dsts[f]), (1, srcs[f], send),
+                     (2, recv, dsts[f]), (3, srcs[f], recv),
+                     (4, recv, dsts[f]))
+            for which, src, dst in sides:
+                for k in range(npeer if which in (1, 2) else 1):
+                    for s, d in enumerate(_entry_descs(nat, n, f, which, k)):
+                        rec("stage.kind",
+                            f"{tag} n={n} f={f} w={which} k={k} s={s}",
+                            _try(lambda: None if d is None else _stage_kind(
+                                nat, d, which, scale, src, dst)))
+    rec("stage.launches", f"{tag} n=0",
+        _try(lambda: nat.stage_launches(0, 0)))
+    rec("stage.launches", f"{tag} stage=3",
+        _try(lambda: nat.stage_launches(1, 3)))
+    for n in SOA_NS:
+        aos = AOS0 + off(2)
+        fields = [DST0 + (c << 20) + off(c) for c in range(n)]
+        for direction in (native.SOA_SPLIT, native.SOA_JOIN):
+            for stage in range(3):
+                rec("soa.launches", f"{tag} n={n} dir={direction} "
+                    f"stage={stage}",
+                    _try(lambda: [tuple(r) for r in nat.stage_launches_soa(
+                        n, direction, stage, aos, fields)]))
+            # local entries with the fields, staged ones on the array alone
+            staged = 1 if direction == native.SOA_SPLIT else 2
+            for which, fp in ((0, fields), (staged, None)):
+                for k in range(npeer if which else 1):
+                    for s, d in enumerate(_entry_descs(nat, n, 0, which, k)):
+                        rec("soa.kind", f"{tag} n={n} dir={direction} "
+                            f"w={which} k={k} s={s}",
+                            _try(lambda: None if d is None else tuple(
+                                native.copy_kernel_kind_soa(
+                                    d, nat.elem_size, n, direction, aos,
+                                    fp))))
+    rec("soa.launches", f"{tag} n=1",
+        _try(lambda: nat.stage_launches_soa(1, native.SOA_SPLIT, 0)))
+    rec("soa.launches", f"{tag} dir=7",
+        _try(lambda: nat.stage_launches_soa(2, 7, 0)))
+
+
+def record_stage_case(cfg_name, flavour):
+    """Every stage query of one (config, flavour): all ranks, without and
+    with an extra dim, on every pointer variant."""
+    grid, size, di, pi, do, po = CONFIGS[cfg_name]
+    kw, scale = FLAVOURS[flavour]
+    kw = dict(kw)
+    esz = kw.pop("elem_size")
+    if "keep" in kw:
+        kw["keep"] = keep_variants(size)[kw["keep"]][0]
+    topo = Topology(grid)
+    Pi = Pencil(topo, size, di, permute=pi)
+    Po = Pencil(topo, size, do, permute=po)
+    rec = Recorder(STAGE_QUERIES)
+    for extra in ((), (3,)):
+        for rank in range(topo.nranks):
+            for pname, off in POINTERS.items():
+                nat = native.NativePlan(Pi, Po, rank, esz, extra, **kw)
+                nat.elem_size = esz
+                tag = f"e={extra} r={rank} p={pname}"
+                if scale is not None:
+                    rec("stage.meta", f"{tag} set_scale",
+                        _try(lambda: nat.set_scale(*scale)))
+                record_stage_plan(rec, tag, nat, scale, off)
+    return rec
+
+
+def stage_case_names():
+    return [(c, f) for c in STAGE_CONFIGS for f in FLAVOURS]
+
+
+def stage_case_id(c):
+    return f"{c[0]}/{c[1]}"
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--stage", action="store_true",
+                    help="the stage matrix and its fixture, not the planners'")
     ap.add_argument("--write", action="store_true",
                     help="write the fixture from the checked-out code")
     ap.add_argument("--dump", metavar="CASE",
                     help="print the full text of one case, for diffing")
     a = ap.parse_args()
+    if a.stage:
+        names, ident, record = stage_case_names(), stage_case_id, \
+            record_stage_case
+        queries, fixture = STAGE_QUERIES, STAGE_FIXTURE
+    else:
+        names, ident, record = case_names(), case_id, record_case
+        queries, fixture = QUERIES, FIXTURE
     if a.dump:
-        c = next(c for c in case_names() if case_id(c) == a.dump)
-        rec = record_case(*c)
-        for q in QUERIES:
+        c = next(c for c in names if ident(c) == a.dump)
+        rec = record(*c)
+        for q in queries:
             print(f"== {q}\n{rec.text(q)}")
         return
-    cases = {case_id(c): list(record_case(*c).digest()) for c in case_names()}
+    cases = {ident(c): list(record(*c).digest()) for c in names}
     if not a.write:
-        with open(FIXTURE) as fh:
+        with open(fixture) as fh:
             want = json.load(fh)["cases"]
-        bad = [f"{name}: {first_difference(want[name], got)}"
+        bad = [f"{name}: {first_difference(want[name], got, queries)}"
                for name, got in cases.items() if want.get(name) != got]
         print("\n".join(bad) if bad else f"{len(cases)} cases match")
         sys.exit(1 if bad else 0)
@@ -323,12 +503,12 @@ def main():
     dirty = subprocess.run(
         ["git", "status", "--porcelain", "--", "pencilarrays_amd", "include"],
         cwd=REPO, text=True, capture_output=True).stdout.strip()
-    with open(FIXTURE, "w") as fh:
+    with open(fixture, "w") as fh:
         json.dump({"generated_from_commit": commit + ("+dirty" if dirty else ""),
-                   "queries": list(QUERIES), "cases": cases}, fh, indent=0,
+                   "queries": list(queries), "cases": cases}, fh, indent=0,
                   sort_keys=True)
         fh.write("\n")
-    print(f"wrote {len(cases)} cases to {FIXTURE}")
+    print(f"wrote {len(cases)} cases to {fixture}")
 
 
 if __name__ == "__main__":
